@@ -7,9 +7,12 @@ whole shard: gpx_propose_batch_dev (1 M proposals) + gpx_accept_reply_batch_dev 
 synthetic accept-reply votes -> 1 M decisions).  Every input column is resident in HBM before
 the timed region; outputs stay in HBM.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` and
-`cpu_baseline` (the CPU oracle = a restatement of the reference algorithm, "port", timed on a
-bounded sample of the same workload on the host cores).
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run sets up, warms up, times
+exactly --steps steps once and prints the line (--dump-outputs DIR also writes what the last timed step
+computed).  --full adds everything else: three timed regions, `roofline` (a per-kernel profile pass),
+`end_to_end` (the host-pointer and wire legs), `parity_checked` (the engine against the oracle on a
+sample) and `cpu_baseline` (the CPU oracle = a restatement of the reference algorithm, "port", timed on
+a bounded sample of the same workload on the host cores), and for N > 1 the `strong` leg.
 """
 import argparse
 import json
@@ -71,6 +74,8 @@ def alg_bytes_per_vote(k: int) -> float:
 
 
 STRONG_GROUPS, STRONG_K = 1_000_000, 5  # BASELINE config #4: the ONE group space the metric is quoted on
+# --dump-outputs: rows per column at most (12 columns x 2^19 rows x 8 bytes = 48 MB) and the seed of the row sample
+DUMP_MAX_ROWS, DUMP_SEED = 1 << 19, 20240607
 
 # the engine's profile labels name the launch (k_bucket_ar16), rocprofv3 the kernel (k_bucket16<0, 4>)
 PMC_ALIAS = {"k_bucket_ar16": "k_bucket16", "k_bucket_accept16": "k_bucket16", "k_bucket_commit16": "k_bucket16",
@@ -216,12 +221,34 @@ class CoordinatorLeg:
         pool = [[torch.from_numpy(c).to(dev) for c in cols] for cols in host_rounds_]
         del host_rounds_
         self.nv = nv = int(pool[0][0].shape[0])
-        vote_cols = []
-        for r in range(rounds):
+        # the rounds past the pool read their own (slot, max_cp) pair of columns from a ring sized to half the device's free
+        # memory; stage() fills a pair for its round before the round runs, outside every timed region.  When every round
+        # fits (any run of ordinary length) all of them are filled here, once
+        extra = rounds - pool_n
+        ring_n = min(extra, max(1, torch.cuda.mem_get_info(dev)[0] // 2 // (8 * nv))) if extra > 0 else 0
+        ring = [(torch.empty(nv, dtype=torch.int32, device=dev), torch.empty(nv, dtype=torch.int32, device=dev))
+                for _ in range(ring_n)]
+        ring_round = [-1] * ring_n
+        self.span = ring_n if 0 < ring_n < extra else rounds  # rounds one stage() can hold
+
+        def vote_cols(r):
             c = pool[r % pool_n]
-            slot_r = c[3] if r < pool_n else torch.full((nv,), r + 1, dtype=torch.int32, device=dev)
-            maxcp_r = c[5] if r < pool_n else torch.full((nv,), r, dtype=torch.int32, device=dev)
-            vote_cols.append([c[0], c[1], c[2], slot_r, c[4], maxcp_r])
+            if r < pool_n:
+                return c
+            s, m = ring[(r - pool_n) % ring_n]
+            return [c[0], c[1], c[2], s, c[4], m]
+
+        def stage(r0, r1):
+            assert r1 - r0 <= self.span, (r0, r1, self.span)
+            with torch.cuda.stream(tstream):  # behind the engine's launches of the rounds that read the pair before
+                for r in range(max(r0, pool_n), r1):
+                    i = (r - pool_n) % ring_n
+                    if ring_round[i] != r:
+                        ring[i][0].fill_(r + 1)
+                        ring[i][1].fill_(r)
+                        ring_round[i] = r
+        self.stage = stage
+        stage(pool_n, pool_n + ring_n)
         g_all = torch.arange(G, dtype=torch.int32, device=dev)
         i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)  # noqa: E731
         u8 = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)  # noqa: E731
@@ -236,7 +263,7 @@ class CoordinatorLeg:
             eng.call_dev("propose_batch", G, P(g_all), 0, P(p_slot), P(p_bnum), P(p_bcoord), P(p_med), P(p_st))
 
         def reply_call(r):
-            c = vote_cols[r]
+            c = vote_cols(r)
             eng.call_dev("accept_reply_batch", nv, P(c[0]), P(c[1]), P(c[2]), P(c[3]), P(c[4]), P(c[5]),
                          P(d_g), P(d_s), P(d_b), P(d_c), P(d_m), P(d_k), n_out[r:].data_ptr(), P(v_st))
 
@@ -253,7 +280,8 @@ class CoordinatorLeg:
             lib, VP = eng.lib, C.c_void_p
             f_p, f_r = lib.fn["propose_batch_dev"], lib.fn["accept_reply_batch_dev"]
             a_p = (eng.h, G, VP(P(g_all)), None, VP(P(p_slot)), VP(P(p_bnum)), VP(P(p_bcoord)), VP(P(p_med)), VP(P(p_st)))
-            a_r = {r: (eng.h, nv, *[VP(P(t)) for t in vote_cols[r]], VP(P(d_g)), VP(P(d_s)), VP(P(d_b)), VP(P(d_c)), VP(P(d_m)),
+            stage(r0, r1)
+            a_r = {r: (eng.h, nv, *[VP(P(t)) for t in vote_cols(r)], VP(P(d_g)), VP(P(d_s)), VP(P(d_b)), VP(P(d_c)), VP(P(d_m)),
                        VP(P(d_k)), VP(n_out[r:].data_ptr()), VP(P(v_st))) for r in range(r0, r1)}
 
             def propose_prepared(r):
@@ -263,7 +291,12 @@ class CoordinatorLeg:
                 lib.check(f_r(*a_r[r]), "accept_reply_batch_dev")
             return propose_prepared, reply_prepared
         self.prepared = prepared
-        self._keep = (vote_cols, g_all, p_slot, p_bnum, p_bcoord, p_med, d_g, d_b, d_c, d_m, v_st)
+        self._keep = (pool, ring, g_all, p_slot, p_bnum, p_bcoord, p_med, d_g, d_b, d_c, d_m, v_st)
+        # what a caller of the step receives (the columns the most recent step wrote), by --dump-outputs' file names
+        self.outputs = {"propose_slot": p_slot, "propose_bnum": p_bnum, "propose_bcoord": p_bcoord,
+                        "propose_median_cp": p_med, "propose_status": p_st,
+                        "decided_gidx": d_g, "decided_slot": d_s, "decided_bnum": d_b, "decided_bcoord": d_c,
+                        "decided_median_cp": d_m, "decided_kind": d_k, "vote_status": v_st}
 
     @staticmethod
     def promise_mask(args):
@@ -281,6 +314,7 @@ class CoordinatorLeg:
         apart per CALL: {"propose_batch": {kernel: (launches, ms)}, "accept_reply_batch": {...}}."""
         eng, torch = self.eng, self.torch
         per_call = {"propose_batch": {}, "accept_reply_batch": {}}
+        self.stage(first_round, first_round + psteps)
         eng.sync()
         for r in range(first_round, first_round + psteps):
             for name, call in (("propose_batch", self.propose_call), ("accept_reply_batch", self.reply_call)):
@@ -297,29 +331,38 @@ class CoordinatorLeg:
     def run_timed(self, warmup, steps, reps=1):
         """The driver's contract, `reps` times over: warm-up once, then per repetition barrier + synchronize, EXACTLY
         `steps` steps, synchronize + barrier, MAX over ranks.  self.elapsed = the MEDIAN repetition (what `value` and
-        `ms_per_step` are computed from), self.elapsed_all = every repetition's."""
+        `ms_per_step` are computed from), self.elapsed_all = every repetition's.  A repetition longer than the rounds
+        the device holds at once (self.span) is timed in spans, the clock stopped while stage() fills the next one."""
         torch, dist, eng, step, dev, world, G = self.torch, self.dist, self.eng, self.step, self.dev, self.world, self.G
-        for r in range(warmup):
-            step(r)
+        span = self.span
+        for r0 in range(0, warmup, span):
+            self.stage(r0, min(r0 + span, warmup))
+            for r in range(r0, min(r0 + span, warmup)):
+                step(r)
         self.elapsed_all, self.gpu_ms_all = [], []
         for rep in range(reps):
             first = warmup + rep * steps
-            eng.sync()
-            torch.cuda.synchronize()
-            self.barrier()
-            torch.cuda.synchronize()
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0 = time.perf_counter()
-            ev0.record()
-            for r in range(first, first + steps):
-                step(r)
-            ev1.record()
-            eng.sync()
-            torch.cuda.synchronize()
-            elapsed = time.perf_counter() - t0  # this rank's K steps, all ranks started together; MAX below
-            self.barrier()
-            torch.cuda.synchronize()
-            self.gpu_ms_all.append(ev0.elapsed_time(ev1))
+            elapsed = gpu_ms = 0.0
+            for r0 in range(first, first + steps, span):
+                r1 = min(r0 + span, first + steps)
+                self.stage(r0, r1)
+                eng.sync()
+                torch.cuda.synchronize()
+                self.barrier()
+                torch.cuda.synchronize()
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                ev0.record()
+                for r in range(r0, r1):
+                    step(r)
+                ev1.record()
+                eng.sync()
+                torch.cuda.synchronize()
+                elapsed += time.perf_counter() - t0  # this rank's K steps, all ranks started together; MAX below
+                self.barrier()
+                torch.cuda.synchronize()
+                gpu_ms += ev0.elapsed_time(ev1)
+            self.gpu_ms_all.append(gpu_ms)
             if self.coll:
                 t = torch.tensor([elapsed], dtype=torch.float64, device=self.cdev)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -356,6 +399,30 @@ class CoordinatorLeg:
         else:
             self.decisions_total = decisions_local
             self.votes_total = self.nv * steps
+
+    def dump_outputs(self, out_dir, last_round):
+        """--dump-outputs: the outputs of round `last_round` (the last timed step, nothing launched since) as
+        out_dir/<name>.npy in float64 - exact for every int32 / uint8 value.  A column longer than DUMP_MAX_ROWS is
+        written as the rows of a fixed seeded sample (sorted row numbers, the same for every column of that length), so
+        that the files stay under 64 MB in all and two builds given the same arguments are compared row for row."""
+        eng, torch = self.eng, self.torch
+        eng.sync()
+        torch.cuda.synchronize()
+        n_dec = int(self.n_out[last_round].item())
+        if n_dec < 0:  # GPX_LAZY_OUTPUTS (--runs): this call's outputs are still parked; make them dense, count rewritten
+            eng.compact_last_dev()
+            eng.sync()
+            n_dec = int(self.n_out[last_round].item())
+        lengths = {"propose": self.G, "decided": n_dec, "vote": self.nv}
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "n_decided.npy"), np.array([n_dec], np.float64))
+        samples = {}
+        for name, t in self.outputs.items():
+            n = lengths[name.split("_")[0]]
+            if n > DUMP_MAX_ROWS and n not in samples:
+                samples[n] = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ROWS, replace=False))).to(self.dev)
+            col = t[:n] if n <= DUMP_MAX_ROWS else t[samples[n]]
+            np.save(os.path.join(out_dir, name + ".npy"), col.cpu().numpy().astype(np.float64))
 
     def close(self):
         self.eng.sync()
@@ -680,7 +747,17 @@ def main():
     ap.add_argument("--mix", action="store_true", help="adversarial mix (dups / stale / higher ballot)")
     ap.add_argument("--stream", choices=("survey", "pcg64"), default="survey",
                     help="survey: SURVEY.md 8(d)'s generator (xorshift64* + Fisher-Yates, in C); pcg64: the numpy one of the tests")
-    ap.add_argument("--profile-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well: three timed regions, the per-kernel "
+                         "profile pass (`roofline`), the end-to-end legs, the parity check against the oracle, the CPU "
+                         "baseline and, for N > 1, the strong-scaling leg.  A plain run times --steps steps once and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (proposal, decision and vote "
+                         "status columns of rank 0) as DIR/<name>.npy in float64; columns longer than %d rows as a fixed "
+                         "seeded sample of rows" % DUMP_MAX_ROWS)
+    ap.add_argument("--profile-steps", type=int, default=None, help="steps of the per-kernel profile pass (default: 5 "
+                                                                    "with --full, else 0)")
     ap.add_argument("--cpu-rounds", type=int, default=8)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline leg (0 = every host core)")
@@ -701,9 +778,10 @@ def main():
                     help="N > 1 only: skip the second timed leg on BASELINE config #4's fixed space (the `strong` object)")
     ap.add_argument("--no-promise", action="store_true",
                     help="do not declare the proposal batches ordered (gpx_engine_set_ordered_batches)")
-    ap.add_argument("--timed-regions", type=int, default=3,
+    ap.add_argument("--timed-regions", type=int, default=None,
                     help="the timed region (exactly --steps steps between barrier + synchronize) is run this many times; "
-                         "ms_per_step / value are the median region's, ms_per_step_spread has them all")
+                         "ms_per_step / value are the median region's, ms_per_step_spread has them all (default: 3 "
+                         "with --full, else 1)")
     ap.add_argument("--pool", type=int, default=96,
                     help="independently seeded rounds kept in HBM (72 MB each at 1 M groups x 3): every step of the default "
                          "run has its own; a longer run reuses them modulo this")
@@ -787,12 +865,15 @@ def main():
     from gigapaxos_amd import Engine, hri_create, load_hip, streams, S_OK
 
     K = args.k
-    steps, warmup, psteps = args.steps, args.warmup, args.profile_steps
-    REPS = max(1, args.timed_regions)
+    steps, warmup = args.steps, args.warmup
+    psteps = args.profile_steps if args.profile_steps is not None else (5 if args.full else 0)
+    REPS = max(1, args.timed_regions if args.timed_regions is not None else (3 if args.full else 1))
     collectives = world > 1 or args.force_collectives
     leg = CoordinatorLeg(args, torch, dist, dev, local_rank, rank, world, args.groups, K, args.split_global,
                          rounds=warmup + REPS * steps + psteps)
     leg.run_timed(warmup, steps, REPS)
+    if args.dump_outputs and rank == 0:
+        leg.dump_outputs(args.dump_outputs, warmup + REPS * steps - 1)
     eng, step, rounds = leg.eng, leg.step, leg.rounds
     leg_pool_rounds = leg.pool_rounds
     G, G_global, nv, nv_round, members, mem, cfg_id = leg.G, leg.G_global, leg.nv, leg.nv_round, leg.members, leg.mem, leg.cfg_id
@@ -873,7 +954,7 @@ def main():
     # ---- N > 1: the shape BASELINE's metric is quoted on - ONE space of 1 M groups, 5 replicas, hash-sharded over
     # the ranks (config #4): total work fixed, so this is the strong-scaling figure beside the weak `value` -------
     strong = None
-    if collectives and not args.split_global and not args.no_strong_leg:
+    if args.full and collectives and not args.split_global and not args.no_strong_leg:
         leg.close()
         sleg = CoordinatorLeg(args, torch, dist, dev, local_rank, rank, world, STRONG_GROUPS, STRONG_K, True,
                               rounds=warmup + steps, mix=False)
@@ -889,7 +970,7 @@ def main():
     # ---- end to end through the HOST-pointer entry points (what a JNI caller with direct ByteBuffers
     # gets): every input column crosses PCIe in, every output column comes back; never `value` -------
     end_to_end = None
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         end_to_end = end_to_end_leg(args, torch, dev, local_rank, G, K, nv, nv_round, members, mem, cfg_id)
         if not args.no_wire_leg and not args.mix and not args.runs and not args.sorted:
             end_to_end["wire"] = wire_end_to_end_leg(args, torch, dev, local_rank, G, K, end_to_end["link"])
@@ -897,7 +978,7 @@ def main():
     # ---- CPU baseline: the oracle (port of the reference algorithm) on the host cores ---
     cpu_baseline = None
     parity_checked = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from tests.oracle_binding import load_oracle
 
         eo = Engine(load_oracle(), 100, G, kmax=K, window=8)

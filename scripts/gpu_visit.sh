@@ -101,7 +101,7 @@ for step in "$@"; do
     ;;
   lines)
     for i in $(seq 1 "${a:-1}"); do
-      timeout 300 python bench.py $(sp "$b") --no-cpu-baseline --no-end-to-end 2>/dev/null | python scripts/bench_line.py "[$(sp "$b")]"
+      timeout 300 python bench.py $(sp "$b") --full --no-cpu-baseline --no-end-to-end 2>/dev/null | python scripts/bench_line.py "[$(sp "$b")]"
     done | tee -a "$OUT/lines.txt"
     ;;
   kt)

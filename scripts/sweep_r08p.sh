@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6, last session: ordered proposals, records per lane of k_propose_one (1 = GPX_PROPOSE_TWO_MIN out of reach)
-line() { python bench.py --no-cpu-baseline --no-end-to-end --steps 20 "$@" 2>/dev/null | python scripts/bench_line.py "[$TAG $*]"; }
+line() { python bench.py --full --no-cpu-baseline --no-end-to-end --steps 20 "$@" 2>/dev/null | python scripts/bench_line.py "[$TAG $*]"; }
 for rep in 1 2 3; do
   TAG="R=1" GPX_PROPOSE_TWO_MIN=2000000000 line
   TAG="R=2" line

@@ -4,7 +4,7 @@
 for rep in $(seq 1 ${SWEEP_REPS:-1}); do
 for f in scratch/variants/*.so; do
   echo "== $f $* $SWEEP_ENV"
-  env $SWEEP_ENV GPX_HIP_LIB=$PWD/$f python bench.py --no-cpu-baseline --no-end-to-end --steps 20 "$@" 2>&1 | python -c "
+  env $SWEEP_ENV GPX_HIP_LIB=$PWD/$f python bench.py --full --no-cpu-baseline --no-end-to-end --steps 20 "$@" 2>&1 | python -c "
 import sys,json
 txt=sys.stdin.read().strip().splitlines()
 try:

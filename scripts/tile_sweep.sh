@@ -4,7 +4,7 @@
 line() { # $1 = tag, rest = bench args; environment of the caller
   local tag=$1
   shift
-  timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-end-to-end "$@" 2>/dev/null | python scripts/bench_line.py "[$tag $*]"
+  timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-end-to-end "$@" 2>/dev/null | python scripts/bench_line.py "[$tag $*]"
 }
 if [ $# -gt 0 ]; then SHAPES=("$@"); else SHAPES=("" "--k 5" "--sorted" "--mix" "--groups 125000 --k 5" "--groups 500000"); fi
 for shape in "${SHAPES[@]}"; do

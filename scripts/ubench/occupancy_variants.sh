@@ -10,7 +10,7 @@ cd "$(dirname "$0")/../.."
 for f in "" scripts/ubench/variants/libgpx_*.so; do
   echo "== ${f:-product build}"
   if [ -n "$f" ]; then export GPX_HIP_LIB=$PWD/$f; else unset GPX_HIP_LIB; fi
-  timeout 200 python bench.py --no-cpu-baseline --no-end-to-end 2>/dev/null | python -c "
+  timeout 200 python bench.py --full --no-cpu-baseline --no-end-to-end 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print(d['ms_per_step'], {k: round(v*1e3,1) for k,v in d['roofline']['kernels_ms_per_step'].items()}, d.get('parity_checked'))"
 done

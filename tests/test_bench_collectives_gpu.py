@@ -26,7 +26,7 @@ def test_nccl_branch_with_a_world_of_one(hip_lib):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-                        "--force-collectives", "--steps", "4", "--warmup", "2", "--profile-steps", "1", "--groups", "200000",
+                        "--force-collectives", "--full", "--steps", "4", "--warmup", "2", "--profile-steps", "1", "--groups", "200000",
                         "--no-cpu-baseline", "--no-end-to-end"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -33,6 +33,7 @@
 #include "gpx_small.hip.h"
 #include "gpx_route.hip.h"
 #include "gpx_wire.hip.h"
+#include "gpx_wire_accept.hip.h"
 #include "gpx_elect.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
@@ -316,6 +317,7 @@ struct gpx_engine {
   uint8_t* w_stage = nullptr;      /* staging of BATCHED_ACCEPT_REPLY frames, 188 B per reply */
   long long* w_bucket_bytes = nullptr;
   int32_t* w_ones = nullptr;       /* a column of ones (gpx_request_batch without weights) */
+  AccScratch wa{};                 /* ACCEPT packing (gpx_wire_pack_accepts_dev), rec == nullptr until first use */
 };
 
 namespace {

@@ -94,6 +94,42 @@ int wire_scratch_init(gpx_engine* e) {
   return GPX_OK;
 }
 
+/* scratch of gpx_wire_pack_accepts_dev, sized from max_batch on its first call (about 100 bytes per record) */
+int wire_accept_init(gpx_engine* e) {
+  if (e->wa.rec) return GPX_OK;
+  const size_t N = (size_t)e->cfg.max_batch, nt = (N + GPX_BLOCK - 1) / GPX_BLOCK + 1;
+  AccScratch& X = e->wa;
+  int rc;
+  if ((rc = dev_alloc(e, &X.lead, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.psize, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.pfol, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.tile_b, nt, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.tile_f, nt, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.tile_k, nt, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.fd, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.flist, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.fsorted, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.fpos, N, false)) != GPX_OK) return rc;
+  if ((rc = dev_alloc(e, &X.n_members, 1, true)) != GPX_OK) return rc;
+  AccRec* rec = nullptr;
+  if ((rc = dev_alloc(e, &rec, N, false)) != GPX_OK) return rc;
+  X.rec = rec; /* last: marks the scratch complete */
+  return GPX_OK;
+}
+
+AccIn acc_in(gpx_engine* h, int32_t n_frames, const uint8_t* frames, const int64_t* frame_off, int32_t n_req,
+             const int32_t* r_frame) {
+  AccIn I;
+  memset(&I, 0, sizeof(I));
+  I.frames = frames;
+  I.foff = (const long long*)frame_off;
+  I.n_frames = n_frames;
+  I.n_req = n_req;
+  I.r_frame = r_frame;
+  I.my_id = h->cfg.my_id;
+  return I;
+}
+
 }  // namespace
 
 extern "C" {
@@ -794,6 +830,71 @@ int gpx_wire_pack_commits(gpx_engine* h, int32_t n, const int32_t* d_gidx, const
     D2H(f_gidx, dfg, m * 4);
     HIPCHK(hipStreamSynchronize(h->sB));
   }
+  return GPX_OK;
+}
+
+int gpx_wire_request_sizes_dev(gpx_engine* h, int32_t n_frames, const uint8_t* frames, const int64_t* frame_off,
+                               int32_t n, const int32_t* r_frame, int32_t* est_bytes, int32_t* weight) {
+  int rc = check_batch(h, n);
+  if (rc != GPX_OK) return rc;
+  if (n_frames < 0) return GPX_EINVAL;
+  if (n == 0) return GPX_OK;
+  if (!frames || !frame_off || !r_frame || !est_bytes || !weight) return GPX_EINVAL;
+  h->stream = h->sB;
+  const AccIn I = acc_in(h, n_frames, frames, frame_off, n, r_frame);
+  LAUNCH(h, "k_acc_req_sizes", k_acc_req_sizes, grid_for(n), I, est_bytes, weight);
+  HIPCHK(hipGetLastError());
+  return GPX_OK;
+}
+
+int gpx_wire_pack_accepts_dev(gpx_engine* h, int32_t n_frames, const uint8_t* frames, const int64_t* frame_off_in,
+                              int32_t n_req, const int32_t* r_frame, const int32_t* leader, int32_t n,
+                              const int32_t* n_dev, const int32_t* b_gidx, const int32_t* b_leader,
+                              const int32_t* b_count, const int32_t* slot, const int32_t* bnum, const int32_t* bcoord,
+                              const int32_t* median_cp, const uint8_t* status, uint8_t* out, int64_t cap_bytes,
+                              int64_t* frame_off, int32_t* frame_len, int32_t* f_gidx, int32_t* f_batch,
+                              int32_t* frame_of, int32_t* n_frames_out, int64_t* n_bytes) {
+  int rc = check_batch(h, n);
+  if (rc != GPX_OK) return rc;
+  if ((rc = check_batch(h, n_req)) != GPX_OK) return rc;
+  if (n_frames < 0 || cap_bytes < 0 || !n_frames_out || !n_bytes) return GPX_EINVAL;
+  if (n == 0) {
+    HIPCHK(hipMemsetAsync(n_frames_out, 0, sizeof(int32_t), h->sB));
+    HIPCHK(hipMemsetAsync(n_bytes, 0, sizeof(int64_t), h->sB));
+    return GPX_OK;
+  }
+  if (!b_gidx || !slot || !bnum || !bcoord || !median_cp || !status || !out || !frame_off || !frame_len || !f_gidx ||
+      !f_batch || ((uintptr_t)out & 3) || (n_req > 0 && (!frames || !frame_off_in || !r_frame)))
+    return GPX_EINVAL;
+  if ((rc = wire_accept_init(h)) != GPX_OK) return rc;
+  AccIn I = acc_in(h, n_frames, frames, frame_off_in, n_req, r_frame);
+  I.leader = leader;
+  I.n = n;
+  I.n_dev = n_dev;
+  I.b_gidx = b_gidx;
+  I.b_leader = b_leader;
+  I.b_count = b_count;
+  I.slot = slot;
+  I.bnum = bnum;
+  I.bcoord = bcoord;
+  I.median = median_cp;
+  I.status = status;
+  AccOut O{out, (long long)cap_bytes, (long long*)frame_off, frame_len, f_gidx, f_batch, frame_of, n_frames_out,
+           (long long*)n_bytes};
+  const AccScratch& X = h->wa;
+  h->stream = h->sB;
+  if (n_req > 0) HIPCHK(hipMemsetAsync(X.lead, 0, (size_t)n_req * sizeof(AccLead), h->sB));
+  const int gr = grid_for(std::max(n, n_req)), gp = grid_for(n), gq = grid_for(std::max(n_req, 1));
+  LAUNCH(h, "k_acc_parse", k_acc_parse, gr, I, X);
+  LAUNCH(h, "k_acc_size", k_acc_size, gp, I, X);
+  LAUNCH(h, "k_acc_place", k_acc_place, gp, I, X, O);
+  LAUNCH(h, "k_acc_members", k_acc_members, gq, I, X);
+  LAUNCH(h, "k_acc_rank", k_acc_rank, gq, I, X, O);
+  /* copy: persistent workgroups over the 16 KB tiles of what fits cap_bytes (the byte count is still on the
+   * device): eight per CU of the chip's 256 */
+  const long long tiles = (cap_bytes + GPX_WA_TILE - 1) / GPX_WA_TILE;
+  if (tiles > 0) LAUNCH(h, "k_acc_copy", k_acc_copy, (int)std::min<long long>(tiles, 2048), I, X, O);
+  HIPCHK(hipGetLastError());
   return GPX_OK;
 }
 

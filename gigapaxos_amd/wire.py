@@ -414,13 +414,41 @@ def pack_commits_dev(we: "WireEngine", n, n_dev_ptr, dec_ptrs, out_ptr, cap_byte
                  "wire_pack_commits_dev")
 
 
+def request_sizes_dev(we: "WireEngine", n_frames, frames_ptr, off_ptr, n, r_frame_ptr, est_ptr, weight_ptr):
+    """gpx_wire_request_sizes_dev with integer device addresses: the est_bytes / weight columns of
+    gpx_request_batch_dev for n decoded request records (r_frame = gpx_wire_requests.frame)."""
+    we.lib.check(we.lib.fn["wire_request_sizes_dev"](we.e.h, int(n_frames), _VP(int(frames_ptr)), _VP(int(off_ptr)),
+                                                     int(n), _VP(int(r_frame_ptr)), _VP(int(est_ptr)),
+                                                     _VP(int(weight_ptr))), "wire_request_sizes_dev")
+
+
+def pack_accepts_dev(we: "WireEngine", n_frames, frames_ptr, off_ptr, n_req, r_frame_ptr, leader_ptr, n, n_dev_ptr,
+                     batch_ptrs, prop_ptrs, out_ptr, cap_bytes, frame_off_ptr, frame_len_ptr, f_gidx_ptr, f_batch_ptr,
+                     frame_of_ptr, n_frames_ptr, n_bytes_ptr):
+    """gpx_wire_pack_accepts_dev with integer device addresses (0 = NULL where the header allows it);
+    batch_ptrs = (b_gidx, b_leader, b_count) of gpx_request_batch_dev, prop_ptrs = (slot, bnum, bcoord, median_cp,
+    status) of gpx_propose_batch_dev."""
+    v = lambda p: _VP(int(p) or None)  # noqa: E731
+    we.lib.check(we.lib.fn["wire_pack_accepts_dev"](we.e.h, int(n_frames), v(frames_ptr), v(off_ptr), int(n_req),
+                                                    v(r_frame_ptr), v(leader_ptr), int(n), v(n_dev_ptr),
+                                                    *[v(p) for p in batch_ptrs], *[v(p) for p in prop_ptrs],
+                                                    v(out_ptr), int(cap_bytes), v(frame_off_ptr), v(frame_len_ptr),
+                                                    v(f_gidx_ptr), v(f_batch_ptr), v(frame_of_ptr), v(n_frames_ptr),
+                                                    v(n_bytes_ptr)), "wire_pack_accepts_dev")
+
+
 _EXTRA_SIGS = {
     "names_coordinator": [C.c_int32, _VP, C.c_int32, _VP],
     "request_batch": [C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32] + [_VP] * 9,
     "gap_scan": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 5,
     "election_scan": [C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32] + [_VP] * 4,
 }
-_EXTRA_DEV_SIGS = {"request_batch_dev": _EXTRA_SIGS["request_batch"]}
+_EXTRA_DEV_SIGS = {
+    "request_batch_dev": _EXTRA_SIGS["request_batch"],
+    "wire_request_sizes_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP],
+    "wire_pack_accepts_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32] + [_VP] * 10 + [C.c_int64]
+    + [_VP] * 7,
+}
 WIRE_EXPORTED_SYMBOLS += list(_EXTRA_SIGS) + list(_EXTRA_DEV_SIGS)
 _WIRE_SIGS.update(_EXTRA_SIGS)
 _WIRE_DEV_SIGS.update(_EXTRA_DEV_SIGS)

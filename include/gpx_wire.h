@@ -218,6 +218,57 @@ int gpx_wire_pack_accept_replies_dev(gpx_engine* h, int32_t n, const int32_t* gi
                                      int32_t* f_gidx, int32_t* f_dest, int32_t* n_frames /* device */,
                                      int64_t* n_bytes /* device */);
 
+/* ---- encode: proposals -> ACCEPT frames (device pointers only) --------------------------------- */
+
+/*
+ * The request -> ACCEPT path of the coordinator without leaving the device: the REQUEST burst that
+ * gpx_wire_decode_dev read stays in HBM, and
+ *   gpx_wire_decode_dev -> gpx_wire_request_sizes_dev -> gpx_request_batch_dev -> gpx_propose_batch_dev
+ *   -> gpx_wire_pack_accepts_dev
+ * leaves the ACCEPT multicast frames next to it.  (There is no host-pointer form: the CPU oracle has no
+ * twin of these calls.)
+ *
+ * gpx_wire_request_sizes_dev: the est_bytes / weight columns of gpx_request_batch for the request
+ * records of a decoded burst (frames[frame_off[r] .. frame_off[r+1]), r = r_frame[i] =
+ * gpx_wire_requests.frame, n_frames frames): est_bytes[i] = the frame's length, weight[i] = its own
+ * batched count + 1.  A record whose frame does not parse: est_bytes = 0, weight = 1.
+ *
+ * gpx_wire_pack_accepts_dev replaces: RequestPacket.latchToBatch / toArray (RequestPacket.java:
+ * 1090-1150) + AcceptPacket.toBytes (AcceptPacket.java:95-135) for the proposals of one
+ * gpx_propose_batch*_dev call, byte for byte what gpx_host.cpp builds with latchToBatch +
+ * makeAcceptFrame.  Proposal b (b < n, or < *n_dev when n_dev is given) has a frame iff
+ * status[b] == GPX_S_OK; its leader record is L = b_leader[b] (b_leader NULL: L = b), its members L,
+ * then the records i != L with leader[i] == L in ascending i (leader NULL: none; leader[i] < 0:
+ * ignored).
+ *   b_count[b] <= 1 (b_count NULL: all): the leader's frame verbatim, packet type (bytes 4..7) ACCEPT.
+ *   b_count[b] > 1, flattened: the leader's bytes up to its batched count (type patched),
+ *     be32(total), its own batched elements; per follower be32(head + 4), the follower's bytes up to
+ *     its batched count, be32(0), then its own batched elements as top-level elements.
+ *     total = the leader's count + sum over followers of (1 + their count); bytes after a frame's
+ *     batched list are dropped, nested elements are copied as they are.
+ *   then the tail: be32 slot, bnum, bcoord, u8 0 (recovery), be32 median_cp, u8 0 (noCoalesce),
+ *     be32 the engine's my_id (22 bytes).
+ * Frames leave in proposal order: frame f occupies out[frame_off[f] .. + frame_len[f]), frame_off is
+ * 4-byte aligned and the pad bytes are zero; f_batch[f] = b, f_gidx[f] = b_gidx[b], frame_of[b]
+ * (nullable) = f or -1.  No frame for a non-OK proposal, a leader or follower that does not parse, a
+ * later proposal naming the same leader record, or a frame over 2 GB.  *n_frames / *n_bytes = all
+ * frames / the bytes they need (device); frames that do not fit cap_bytes are not written (the caller
+ * sees n_bytes > cap_bytes).  Scratch (about 100 bytes per max_batch record) is allocated by the first
+ * call.
+ */
+int gpx_wire_request_sizes_dev(gpx_engine* h, int32_t n_frames, const uint8_t* frames,
+                               const int64_t* frame_off, int32_t n, const int32_t* r_frame,
+                               int32_t* est_bytes, int32_t* weight);
+int gpx_wire_pack_accepts_dev(gpx_engine* h, int32_t n_frames, const uint8_t* frames,
+                              const int64_t* frame_off_in, int32_t n_req, const int32_t* r_frame,
+                              const int32_t* leader, int32_t n, const int32_t* n_dev,
+                              const int32_t* b_gidx, const int32_t* b_leader, const int32_t* b_count,
+                              const int32_t* slot, const int32_t* bnum, const int32_t* bcoord,
+                              const int32_t* median_cp, const uint8_t* status, uint8_t* out,
+                              int64_t cap_bytes, int64_t* frame_off, int32_t* frame_len,
+                              int32_t* f_gidx, int32_t* f_batch, int32_t* frame_of,
+                              int32_t* n_frames_out /* device */, int64_t* n_bytes /* device */);
+
 /* ---- what leaves together: the batcher's payload bound and cross-group batching ------------- */
 
 /*

@@ -462,9 +462,14 @@ class Engine:
         self.lib.check(self.lib.fn["profile_enable"](self.h, int(enable)), "profile_enable")
 
     def profile_read(self):
-        buf = (GpxKernelStat * 32)()
-        nk = self.lib.check(self.lib.fn["profile_read"](self.h, buf, 32), "profile_read")
-        return {buf[i].name.decode(): (int(buf[i].launches), float(buf[i].total_ms)) for i in range(min(nk, 32))}
+        cap = 32
+        while True:
+            buf = (GpxKernelStat * cap)()
+            nk = self.lib.check(self.lib.fn["profile_read"](self.h, buf, cap), "profile_read")
+            if nk <= cap:
+                break
+            cap = nk  # more kernels than the buffer: read them all
+        return {buf[i].name.decode(): (int(buf[i].launches), float(buf[i].total_ms)) for i in range(nk)}
 
     # -- asynchronous host-pointer path (gpx_*_batch_async / gpx_engine_wait) -------------------------
     class Pending:

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <cassert>
 #include <initializer_list>
 
 #include "gpx_kernels.hip.h"
@@ -1251,9 +1252,18 @@ static bool ar_tiles_call(gpx_engine* e, int32_t n, const int32_t* gidx, const i
                           int32_t* n_out, uint8_t* status) {
   const int32_t nbk = e->nbk16;
   if (nbk > GPX_MAX_BUCKETS || e->shift16 > 10 || e->shift16 < 8) return false;
-  const TileShape ts = tile_shape(e, n, nbk);
+  TileShape ts = tile_shape(e, n, nbk);
+  /* a scatter workgroup keeps at most eight bucket counters per thread (tl_cnt_words), and it needs nbk + 1 of them:
+   * 4,096 buckets take 1024 threads (512 would never write the entry behind bucket 4095 - its run's end) */
+  if (nbk + 1 > ts.NT * 8) ts.NT = 1024;
+  assert(nbk + 1 <= ts.NT * 8);
   const int32_t T = ts.T;
   if ((T != 4096 && T != 8192 && T != 12288 && T != 16384) || (ts.NT != 512 && ts.NT != 1024) || T % (ts.NT * 4)) return false;
+  /* only the shapes k_scatter_tiles is instantiated for (a forced GPX_TILE_T / GPX_TILE_NT may ask for others), in the
+   * LDS that its attribute allows */
+  const int r4 = T / (ts.NT * 4);
+  if (!(ts.NT == 1024 && r4 >= 1 && r4 <= 4) && !(ts.NT == 512 && (r4 == 2 || r4 == 4))) return false;
+  if (GPX_TL_LDS_BYTES(nbk, T, ts.NT) > (size_t)158 * 1024) return false;
   const int32_t nwg = (n + T - 1) / T;
   if (nwg > GPX_TL_MAXWG) return false;
   const size_t N = (size_t)e->cfg.max_batch;
@@ -1314,13 +1324,13 @@ static bool ar_tiles_call(gpx_engine* e, int32_t n, const int32_t* gidx, const i
 #define GPX_LAUNCH_TILES(NT_, R4_)                                                                                       \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scatter_tiles<NT_, R4_>), dim3(tile_grid(A.nwg)), dim3(NT_), lds, e->stream, n, e->S.G, \
                      e->X, A, gidx, bnum, bcoord, slot, acceptor, max_cp, status)
-    const int r4 = T / (ts.NT * 4);
     if (ts.NT == 1024 && r4 == 4) GPX_LAUNCH_TILES(1024, 4);
     else if (ts.NT == 1024 && r4 == 3) GPX_LAUNCH_TILES(1024, 3);
     else if (ts.NT == 1024 && r4 == 2) GPX_LAUNCH_TILES(1024, 2);
     else if (ts.NT == 1024 && r4 == 1) GPX_LAUNCH_TILES(1024, 1);
     else if (ts.NT == 512 && r4 == 4) GPX_LAUNCH_TILES(512, 4);
-    else GPX_LAUNCH_TILES(512, 2);
+    else if (ts.NT == 512 && r4 == 2) GPX_LAUNCH_TILES(512, 2);
+    else assert(!"k_scatter_tiles: no instantiation for this shape (refused above)");
 #undef GPX_LAUNCH_TILES
   }
   const Stage16 O{(int32_t*)e->X.o_rec, (int64_t)N};

@@ -22,11 +22,13 @@ def assert_same_state(ea, eb, groups):
         assert da.tolist() == db.tolist(), f"group {g} state differs:\n{da.tolist()}\n{db.tolist()}"
 
 
-def create_mixed_groups(ea, eb, G, kmax, node_ids, rng, slot_base=1, my_id=None):
+def create_mixed_groups(ea, eb, G, kmax, node_ids, rng, slot_base=1, my_id=None, gmap=None):
     """Groups of varying size k <= kmax, members drawn (sorted) from node_ids; half created with
-    createHRI rows, half with regular-creation rows; coordinator = my_id for ~2/3 of them."""
+    createHRI rows, half with regular-creation rows; coordinator = my_id for ~2/3 of them.  gmap: the
+    table rows (gidx) of the G groups, G ascending entries (default: rows 0 .. G-1)."""
     my_id = ea.my_id if my_id is None else my_id
-    gidx = np.arange(G, dtype=np.int32)
+    gidx = np.arange(G, dtype=np.int32) if gmap is None else np.asarray(gmap, np.int32)
+    assert gidx.shape[0] == G
     members = np.zeros((G, kmax), np.int32)
     ks = np.zeros(G, np.uint8)
     rows = make_hri(G)
@@ -51,11 +53,31 @@ def create_mixed_groups(ea, eb, G, kmax, node_ids, rng, slot_base=1, my_id=None)
 
 
 def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=None, p_stop=0.01,
-         ordered=False):
-    """Random interleaving of propose / accept / accept_reply / commit batches with colliding
-    slots, duplicate votes, stale and higher ballots, non-member acceptors, unknown groups."""
+         ordered=False, gmap=None, min_batch=1):
+    """Random interleaving of propose / accept / accept_reply / commit / prepare batches with colliding
+    slots, duplicate votes, stale and higher ballots, non-member acceptors, unknown groups.
+
+    gmap: the table rows (gidx, ascending) of the G fuzzed groups - a hot set inside a larger table; the
+    out-of-table indices stay out of the table (-1, max_groups, max_groups + 5).  min_batch: the smallest
+    batch drawn.  With the defaults the driver draws exactly the random numbers it always drew.  Returns, per
+    operation, the set of statuses the engines answered with."""
     my_id = ea.my_id if my_id is None else my_id
     nodes = np.array(list(node_ids) + [my_id - 7], np.int32)  # last = never a member
+    if gmap is None:
+        to_row = None
+        rows_of = np.arange(G)
+    else:
+        gm = np.asarray(gmap, np.int32)
+        assert gm.shape[0] == G and (np.diff(gm) > 0).all()
+        Gt = int(ea.cfg.max_groups)
+        lut = np.concatenate([gm, np.array([-1, Gt, Gt + 5], np.int32)])
+
+        def to_row(f):
+            # fuzz index -> table row: -1 -> -1, G -> max_groups, G + 5 -> max_groups + 5
+            f = np.asarray(f, np.int64)
+            return lut[np.where(f < 0, G + 0, np.where(f == G, G + 1, np.where(f > G, G + 2, f)))].astype(np.int32)
+        rows_of = gm
+    seen = {op: set() for op in ("propose", "accept", "accept_reply", "commit", "prepare")}
 
     def gids(n):
         g = rng.integers(0, G, n).astype(np.int32)
@@ -84,18 +106,20 @@ def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=Non
 
     for step in range(steps):
         op = rng.integers(0, 5)
-        n = int(rng.integers(1, batch + 1))
-        g = gids(n)
+        n = int(rng.integers(min_batch, batch + 1))
+        f = gids(n)
+        g = f if to_row is None else to_row(f)
         if op == 0:
-            # keep every group's proposal frontier inside the slot span the votes can reach, so
-            # the engine's fixed window never fills (the oracle's maps are unbounded): at most one
-            # proposal per group per batch, only for groups whose next slot is still in range
-            rows, _ = ea.snapshot(np.arange(G))
+            # keep most groups' proposal frontier inside the slot span the votes can reach: at most one
+            # proposal per group per batch, only for groups whose next slot is still in range.  (The oracle
+            # models the engine's window refusals; this only keeps the votes relevant.  Windows smaller than
+            # the span still fill and refuse with GPX_S_WINDOW.)
+            rows, _ = ea.snapshot(rows_of)
             room = (rows["next_proposal_slot"].astype(np.int64) - slot_base) < span - 2
-            ok = (g < 0) | (g >= G)
+            ok = (f < 0) | (f >= G)
             inr = ~ok
-            ok[inr] = room[g[inr]] | (rows["has_coord"][g[inr]] == 0)
-            _, first = np.unique(g, return_index=True)
+            ok[inr] = room[f[inr]] | (rows["has_coord"][f[inr]] == 0)
+            _, first = np.unique(f, return_index=True)
             uniq = np.zeros(n, bool)
             uniq[first] = True
             g = g[ok & uniq]
@@ -106,6 +130,7 @@ def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=Non
             ra, rb = ea.propose(g, stop), eb.propose(g, stop)
             for x, y, nm in zip(ra, rb, ("slot", "bnum", "bcoord", "median", "status")):
                 assert x.tolist() == y.tolist(), f"step {step} propose {nm}"
+            seen["propose"].update(np.unique(ra[4]).tolist())
         elif op == 1:
             bnum, bcoord = ballots(n)
             sl = slots(n)
@@ -115,6 +140,7 @@ def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=Non
             for x, y, nm in zip(ra, rb, ("r_bnum", "r_bcoord", "r_maxcp", "r_flags", "status")):
                 assert x.tolist() == y.tolist(), f"step {step} accept {nm}"
             assert xa.as_tuple_array().tolist() == xb.as_tuple_array().tolist(), f"step {step} accept runs"
+            seen["accept"].update(np.unique(ra[4]).tolist())
         elif op == 2:
             bnum, bcoord = ballots(n)
             sl = slots(n)
@@ -123,6 +149,7 @@ def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=Non
             da, db = ea.accept_reply(g, bnum, bcoord, sl, acc, mcp), eb.accept_reply(g, bnum, bcoord, sl, acc, mcp)
             assert da.as_tuple_array().tolist() == db.as_tuple_array().tolist(), f"step {step} decisions"
             assert da.status.tolist() == db.status.tolist(), f"step {step} ar status"
+            seen["accept_reply"].update(np.unique(da.status).tolist())
         elif op == 4:
             # PREPAREs (view change, acceptor side): ballots around the current ones, so that acks,
             # NACKs and ballot upgrades all occur; firstUndecidedSlot around the live slots
@@ -132,6 +159,7 @@ def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=Non
             for x, y, nm in zip(ra, rb, ("r_bnum", "r_bcoord", "r_gc", "r_flags", "status")):
                 assert x.tolist() == y.tolist(), f"step {step} prepare {nm}"
             assert pa == pb, f"step {step} prepare pvalues"
+            seen["prepare"].update(np.unique(ra[4]).tolist())
         else:
             bnum, bcoord = ballots(n)
             sl = slots(n)
@@ -140,9 +168,11 @@ def fuzz(ea, eb, G, node_ids, rng, steps, batch, slot_base=1, span=40, my_id=Non
             (sa, xa), (sb, xb) = ea.commit(g, bnum, bcoord, sl, med, kind), eb.commit(g, bnum, bcoord, sl, med, kind)
             assert sa.tolist() == sb.tolist(), f"step {step} commit status"
             assert xa.as_tuple_array().tolist() == xb.as_tuple_array().tolist(), f"step {step} commit runs"
-    assert_same_state(ea, eb, range(G))
+            seen["commit"].update(np.unique(sa).tolist())
+    assert_same_state(ea, eb, rows_of)
     ca, cb = ea.counters(), eb.counters()
     assert ca == cb, (ca, cb)
+    return seen
 
 
 def churn_run(engines, G_live, cap, R, k, seed, churn_frac=0.01):

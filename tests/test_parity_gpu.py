@@ -18,8 +18,11 @@ def _accept_reply_path(request, monkeypatch):
     """Accept-reply batches go through the partition pipeline or, with the GPX_TRY_REPLY_RUNS hint (here set
     for every engine through the test switch GPX_TRY_RUNS=1, read at engine creation), first through the
     sorted-runs check (gpx_runs.hip.h): a batch that happens to be a few ascending runs is applied without
-    partition, any other falls back behind it - every case of this file runs both ways."""
+    partition, any other falls back behind it - every case of this file runs both ways.  GPX_SAR_MAX_N=0 under both:
+    a call of up to 1,024 votes would otherwise go to the one-workgroup path (k_ar_tiny, test_small_ar_gpu.py) before
+    the runs check or the partition."""
     monkeypatch.setenv("GPX_TRY_RUNS", "1" if request.param.startswith("sorted") else "0")
+    monkeypatch.setenv("GPX_SAR_MAX_N", "0")
 
 
 NODES = [100, 101, 102, 103, 104, 105, 106, 107]
@@ -32,7 +35,10 @@ def test_fuzz_mixed_ops(hip_lib, oracle_lib, kmax, seed):
     G = 64
     eh, eo = make_pair(hip_lib, oracle_lib, 100, G, kmax, 64)
     create_mixed_groups(eh, eo, G, kmax, nodes, rng)
+    eh.profile(2)
     fuzz(eh, eo, G, nodes, rng, steps=250, batch=300)
+    ran = eh.profile_read()
+    assert "k_ar_tiny" not in ran and "k_emit_dec16" in ran, sorted(ran)
 
 
 @pytest.mark.parametrize("kmax,G,seed", [(3, 48, 21), (5, 700, 22), (3, 3000, 23)])

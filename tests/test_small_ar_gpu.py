@@ -133,7 +133,7 @@ def test_skewed_small_calls(hip_lib, oracle_lib, shape, n):
     eh.close(), eo.close()
 
 
-@pytest.mark.parametrize("K,G,seed", [(3, 40, 1), (5, 3000, 2), (16, 500, 3), (3, 200_000, 4)])
+@pytest.mark.parametrize("K,G,seed", [(3, 40, 1), (5, 3000, 2), (8, 2000, 5), (16, 500, 3), (3, 200_000, 4)])
 def test_small_call_fuzz(hip_lib, oracle_lib, K, G, seed):
     """The mixed-operation fuzz of test_parity_gpu.py (colliding slots, duplicate votes, stale and higher ballots,
     non-member acceptors, unknown groups): every vote batch has at most 1,000 votes - the one-launch path."""

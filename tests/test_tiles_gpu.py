@@ -10,6 +10,7 @@ import pytest
 
 from gigapaxos_amd import hri_create, streams, S_OK
 from tests.parity_common import make_pair, assert_same_state
+from tests.geometry_common import ar_kernels, ar_route, geometry
 from tests.test_fullsize_gpu import _same, _vote_stream_parity
 
 pytestmark = pytest.mark.gpu
@@ -109,13 +110,33 @@ def test_larger_groups_through_tiles(hip_lib, oracle_lib, G, k):
     eo.close()
 
 
-@pytest.mark.parametrize("T,NT", [(4096, 512), (8192, 512), (8192, 1024), (12288, 1024), (16384, 1024), (4096, 1024)])
+@pytest.mark.parametrize("T,NT", [(4096, 512), (8192, 512), (8192, 1024), (12288, 1024), (16384, 1024), (4096, 1024),
+                                  (12288, 512), (16384, 512)])
 def test_every_tile_shape(hip_lib, oracle_lib, monkeypatch, T, NT):
     """The scatter kernel's instantiations (votes and threads per workgroup; chosen per call otherwise), each on a call
-    whose last tile is partly filled."""
+    whose last tile is partly filled.  12,288 and 16,384 votes on 512 threads have no instantiation: such a forced shape
+    is refused, and the call takes the partition front end."""
     monkeypatch.setenv("GPX_TILE_T", str(T))
     monkeypatch.setenv("GPX_TILE_NT", str(NT))
     _vote_stream_parity(hip_lib, oracle_lib, 300_000, 3, True, R=2)
+    G, k = 300_000, 3
+    route = ar_route(geometry(G, k), G * k, force_T=T, force_NT=NT)
+    assert route[0] == ("partition" if (T, NT) in ((12288, 512), (16384, 512)) else "tiles"), route
+    eh, eo = make_pair(hip_lib, oracle_lib, 101, G, k, 8, max_batch=G * k + 4096)
+    mem = np.tile(np.array([100, 101, 102], np.int32), (G, 1))
+    for e in (eh, eo):
+        assert (e.create_groups(np.arange(G), mem, k, hri_create(G, k, 101)) == S_OK).all()
+    g = np.arange(G, dtype=np.int32)
+    for x, y in zip(eh.propose(g), eo.propose(g)):
+        assert (x == y).all()
+    cols = streams.vote_round(G, [100, 101, 102], 0, 101, config_id=3, mix=False)
+    eh.profile(2)
+    dh, do = eh.accept_reply(*cols), eo.accept_reply(*cols)
+    ran = eh.profile_read()
+    _same(dh, do, "profiled call")
+    assert ar_kernels(route) <= set(ran) and ("k_scatter_tiles" in ran) == (route[0] == "tiles"), (route, sorted(ran))
+    eh.close()
+    eo.close()
 
 
 def _lockstep_free_rows(G, k, me, rng):

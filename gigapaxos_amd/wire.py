@@ -414,6 +414,19 @@ def pack_commits_dev(we: "WireEngine", n, n_dev_ptr, dec_ptrs, out_ptr, cap_byte
                  "wire_pack_commits_dev")
 
 
+def pack_accept_replies_dev(we: "WireEngine", n, reply_ptrs, status_ptr, unbatched_ptr, out_ptr, cap_bytes,
+                            frame_off_ptr, frame_len_ptr, f_gidx_ptr, f_dest_ptr, n_frames_ptr, n_bytes_ptr):
+    """gpx_wire_pack_accept_replies_dev with integer device addresses: ONE pass, replies over a per-call limit are
+    left with unbatched = 2 (WireEngine.pack_accept_replies runs the further passes).  reply_ptrs = (gidx, slot,
+    sender, req_id, r_bnum, r_bcoord, r_maxcp); sender, req_id and unbatched may be 0 (NULL)."""
+    v = lambda p: _VP(int(p) or None)  # noqa: E731
+    we.lib.check(we.lib.fn["wire_pack_accept_replies_dev"](we.e.h, int(n), *[v(p) for p in reply_ptrs], v(status_ptr),
+                                                           v(unbatched_ptr), v(out_ptr), int(cap_bytes),
+                                                           v(frame_off_ptr), v(frame_len_ptr), v(f_gidx_ptr),
+                                                           v(f_dest_ptr), v(n_frames_ptr), v(n_bytes_ptr)),
+                 "wire_pack_accept_replies_dev")
+
+
 def request_sizes_dev(we: "WireEngine", n_frames, frames_ptr, off_ptr, n, r_frame_ptr, est_ptr, weight_ptr):
     """gpx_wire_request_sizes_dev with integer device addresses: the est_bytes / weight columns of
     gpx_request_batch_dev for n decoded request records (r_frame = gpx_wire_requests.frame)."""

@@ -104,3 +104,45 @@ def test_window_cells_refuse(oracle_lib, name):
     seen, _ = run_cell(oracle_lib, oracle_lib, CELLS[name])
     for op in CELLS[name]["refused"]:
         assert S_WINDOW in seen[op], (name, op, seen)
+
+
+@pytest.mark.parametrize("G,shift,limits", [(3000, 11, False), (3000, 11, True), (9000, 12, True)])
+def test_wire_geometry_setup_and_first_pass_on_the_oracle(oracle_lib, G, shift, limits):
+    """test_wire_geometry_gpu.py's setup binds every hot-set name, and its restatement of the device form's one pass
+    (first_pass) agrees with the oracle's packer: frames, bytes and unbatched exactly where no per-call limit is hit;
+    where one is, the records it marks 2 are packed by the host form's later passes and the rest match."""
+    from gigapaxos_amd import wire as W
+    from gigapaxos_amd import S_OK, hri_create
+    from tests.test_wire_geometry_gpu import MEMBERS, hot_name, first_pass, _accept_batch
+    geo = geometry(G, 3, shift)
+    rng = np.random.default_rng(G)
+    hot, place = hot_set(G, geo, rng)
+    names = [hot_name(int(x)) for x in hot]
+    assert len(set(names)) == hot.shape[0] and {len(x) for x in names} <= set(range(1, 128))
+    e, _ = make_pair(oracle_lib, oracle_lib, 100, G, 3, 8)
+    assert (e.create_groups(np.arange(G), np.tile(np.array(MEMBERS, np.int32), (G, 1)), 3, hri_create(G, 3, 100)) == S_OK).all()
+    we = W.WireEngine(e)
+    named_rows = np.setdiff1d(hot, hot[5::17]).astype(np.int32)
+    assert (we.bind([hot_name(int(x)) for x in named_rows], named_rows) == S_OK).all()
+    named = np.zeros(G, bool)
+    named[named_rows] = True
+    name_len = np.zeros(G, np.int32)
+    name_len[named_rows] = [len(hot_name(int(x))) for x in named_rows]
+    g, bnum, bcoord, slot, median, sender, big = _accept_batch(hot, place, G, rng)
+    if not limits:
+        keep = g != big
+        g, bnum, bcoord, slot, median, sender = (x[keep] for x in (g, bnum, bcoord, slot, median, sender))
+        bnum, bcoord = bnum % 2, 100 + bcoord % 2
+        sender = np.where(sender == 100, 100, bcoord).astype(np.int32)
+    (rb, rc, rm, _, st), _ = e.accept(g, bnum, bcoord, slot, median)
+    ub, nf, nb = first_pass(g, st, sender, rb, rc, slot, named, name_len)
+    frames, _, _, ub_o, nb_o = we.pack_accept_replies(g, slot, rb, rc, rm, st, sender)
+    assert (ub == 1).any() and (ub == 0).any()
+    if not limits:
+        assert not (ub == 2).any()
+        assert ub.tolist() == ub_o.tolist() and nf == len(frames) and nb == nb_o
+    else:
+        assert (ub[g == big] == 2).any()
+        assert (ub_o[ub == 2] == 0).all() and ub_o[ub != 2].tolist() == ub[ub != 2].tolist()
+        assert nf < len(frames) and nb < nb_o
+    e.close()

@@ -55,6 +55,22 @@ class GpxKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
 
+class GpxPackedVotes(C.Structure):
+    """struct gpx_packed_votes (include/gpx_packed.h)."""
+    _fields_ = [
+        ("n", C.c_int32),
+        ("n_exc", C.c_int32),
+        ("bnum", C.c_int32),
+        ("bcoord", C.c_int32),
+        ("base_slot", C.c_int32),
+        ("base_cp", C.c_int32),
+        ("base_acceptor", C.c_int32),
+        ("reserved", C.c_int32),
+        ("rec", C.c_void_p),
+        ("exc", C.c_void_p),
+    ]
+
+
 # numpy mirror of struct gpx_hri (HotRestoreInfo.java:35-84 minus the name)
 HRI_DTYPE = np.dtype(
     [
@@ -118,13 +134,23 @@ _DEV_SIGS = {
     "accept_reply_batch_async": [C.c_int32] + [_VP] * 3 + [C.c_int32, C.c_int32] + [_VP] * 11 + [C.POINTER(C.c_uint64)],
     "commit_batch_async": [C.c_int32] + [_VP] * 11 + [C.POINTER(C.c_uint64)],
     "engine_wait": [C.c_uint64],
+    # packed votes (include/gpx_packed.h)
+    "votes_unpack_dev": [C.POINTER(GpxPackedVotes)] + [_VP] * 6,
+    "accept_reply_packed_dev": [C.POINTER(GpxPackedVotes)] + [_VP] * 8,
+    "accept_reply_packed_async": [C.POINTER(GpxPackedVotes)] + [_VP] * 8 + [C.POINTER(C.c_uint64)],
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],
 }
 
+# host helpers of the HIP library that take no engine handle (include/gpx_packed.h): name -> full argtypes
+_HOST_SIGS = {
+    "votes_pack": [C.c_int32] + [_VP] * 8 + [C.c_int32, C.POINTER(GpxPackedVotes)],
+    "votes_unpack": [C.POINTER(GpxPackedVotes)] + [_VP] * 6,
+}
+
 EXPORTED_SYMBOLS = (
-    ["abi_version", "last_error", "engine_create"] + list(_SIGS) + list(_DEV_SIGS)
+    ["abi_version", "last_error", "engine_create"] + list(_SIGS) + list(_DEV_SIGS) + list(_HOST_SIGS)
 )
 
 
@@ -169,6 +195,11 @@ class GpxLib:
         for name, args in sigs.items():
             f = getattr(self.lib, prefix + name)
             f.argtypes = [_VP] + args
+            f.restype = C.c_int
+            self.fn[name] = f
+        for name, args in (_HOST_SIGS if device_api else {}).items():
+            f = getattr(self.lib, prefix + name)
+            f.argtypes = args
             f.restype = C.c_int
             self.fn[name] = f
         self.device_api = device_api
@@ -542,6 +573,51 @@ class Engine:
             m = int(no[0])
             return Decisions(dg[:m], ds[:m], db[:m], dc[:m], dm[:m], dk[:m], status)
         return Engine.Pending(self, t.value, (gidx, bnum, bcoord, slot, acceptor, max_cp), finish)
+
+    def accept_reply_packed_async(self, packed, pin_outputs=False):
+        """gpx_accept_reply_packed_async: `packed` is a packed.PackedVotes over host arrays (its records and exception
+        rows cross the link instead of the columns).  Outputs as accept_reply_async."""
+        n = packed.n
+        cap = max(n, 1)
+        mk = Engine.page_array if pin_outputs else np.zeros   # registered outputs: whole pages of their own
+        dg, ds, db, dc, dm = (mk(cap, np.int32) for _ in range(5))
+        dk = mk(cap, np.uint8)
+        status = mk(n, np.uint8)
+        no = mk(1, np.int32)
+        outs = (dg, ds, db, dc, dm, dk, no, status)
+        if pin_outputs:
+            self.host_register(*outs)
+        t = C.c_uint64(0)
+        pv = packed.struct()
+        try:
+            self.lib.check(self.lib.fn["accept_reply_packed_async"](
+                self.h, C.byref(pv), _p(dg), _p(ds), _p(db), _p(dc), _p(dm), _p(dk), _p(no), _p(status), C.byref(t)),
+                "accept_reply_packed_async")
+        except GpxError:
+            if pin_outputs:
+                self.host_unregister(*outs)
+            raise
+
+        def finish():
+            if pin_outputs:
+                self.host_unregister(*outs)
+            m = int(no[0])
+            return Decisions(dg[:m], ds[:m], db[:m], dc[:m], dm[:m], dk[:m], status)
+        return Engine.Pending(self, t.value, (packed,), finish)
+
+    def votes_unpack_dev(self, header, rec_ptr: int, exc_ptr: int, col_ptrs):
+        """gpx_votes_unpack_dev: `header` is a packed.PackedVotes (its fields go by value), rec_ptr / exc_ptr and the six
+        col_ptrs are integer device addresses (0 = NULL)."""
+        pv = header.struct(rec_ptr, exc_ptr)
+        args = [_VP(int(p)) if p else None for p in col_ptrs]
+        self.lib.check(self.lib.fn["votes_unpack_dev"](self.h, C.byref(pv), *args), "votes_unpack_dev")
+
+    def accept_reply_packed_dev(self, header, rec_ptr: int, exc_ptr: int, *out_ptrs):
+        """gpx_accept_reply_packed_dev: records and exception rows at device addresses; out_ptrs = d_gidx, d_slot, d_bnum,
+        d_bcoord, d_median_cp, d_kind, n_out, status as integer device addresses."""
+        pv = header.struct(rec_ptr, exc_ptr)
+        args = [_VP(int(p)) if p else None for p in out_ptrs]
+        self.lib.check(self.lib.fn["accept_reply_packed_dev"](self.h, C.byref(pv), *args), "accept_reply_packed_dev")
 
     def accept_async(self, gidx, bnum, bcoord, slot, median_cp, a_flags=None):
         gidx = _i32(gidx)

@@ -36,6 +36,7 @@
 #include "gpx_wire.hip.h"
 #include "gpx_wire_accept.hip.h"
 #include "gpx_elect.hip.h"
+#include "gpx_packed.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -293,6 +294,10 @@ struct gpx_engine {
     const uint8_t* dev_kind = nullptr;
     int32_t* host_count = nullptr; /* n_out / n_runs of the caller */
     int32_t n = 0;                 /* records of the call: the capacity of every output column (gpx.h) */
+    /* gpx_accept_reply_packed_async: where the call's records ([max_batch][2]) and exception rows ([max_batch / 4][8])
+     * land before k_votes_unpack makes i32[0..5] of them (first packed call) */
+    uint32_t* pk_rec = nullptr;
+    int32_t* pk_exc = nullptr;
   } as[GPX_ASYNC_DEPTH_MAX];
   int async_depth = GPX_ASYNC_DEPTH; /* sets in use (GPX_ASYNC_DEPTH=n, up to GPX_ASYNC_DEPTH_MAX) */
   hipStream_t s_in = nullptr;
@@ -319,6 +324,7 @@ struct gpx_engine {
   long long* w_bucket_bytes = nullptr;
   int32_t* w_ones = nullptr;       /* a column of ones (gpx_request_batch without weights) */
   AccScratch wa{};                 /* ACCEPT packing (gpx_wire_pack_accepts_dev), rec == nullptr until first use */
+  int32_t* pk_cols = nullptr;      /* gpx_accept_reply_packed_dev: six unpacked columns, 16-byte aligned (first use) */
 };
 
 namespace {
@@ -2690,6 +2696,100 @@ int gpx_accept_reply_batch_async(gpx_engine* h, int32_t n, const int32_t* gidx, 
         hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(n)), dim3(GPX_BLOCK), 0, fs, n, common_bcoord, a.i32[2]);
       }
     }
+    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
+    h->lazy_override = 0; /* k_copy_out reads the count on the device: dense columns, always */
+    rc = gpx_accept_reply_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5], a.i32[6],
+                                    a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.cnt, a.u8[1]);
+    h->lazy_override = -1;
+    if (rc != GPX_OK) return async_fail(h, a, rc);
+    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
+    if (status) {
+      uint8_t* hb[1] = {status};
+      const uint8_t* db[1] = {a.u8[1]};
+      if ((rc = async_dense_out(h, a, n, 0, nullptr, nullptr, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
+    }
+    a.ncols = 5;
+    int32_t* hc[5] = {d_gidx, d_slot, d_bnum, d_bcoord, d_median_cp};
+    for (int k = 0; k < 5; k++) {
+      a.host_col[k] = hc[k];
+      a.dev_col[k] = a.i32[6 + k];
+    }
+    a.host_kind = d_kind;
+    a.dev_kind = a.u8[0];
+  }
+  rc = async_submit(h, a, n > 0, ticket);
+  return rc == GPX_OK ? rc : async_fail(h, a, rc);
+}
+
+/* ---- packed votes (include/gpx_packed.h) ---- */
+static int packed_check(gpx_engine* h, const gpx_packed_votes* pv) {
+  if (!h || !pv || pv->n < 0 || pv->n_exc < 0) return GPX_EINVAL;
+  if ((pv->n > 0 && !pv->rec) || (pv->n_exc > 0 && !pv->exc)) return GPX_EINVAL;
+  if (pv->n > h->cfg.max_batch || pv->n_exc > pv->n / GPX_PACKED_EXC_DIV) return GPX_ECAPACITY;
+  return GPX_OK;
+}
+/* entries of one unpacked column: max_batch rounded up to whole 16-byte stores */
+static size_t packed_col_stride(const gpx_engine* h) { return ((size_t)h->cfg.max_batch + 3) & ~(size_t)3; }
+
+int gpx_votes_unpack_dev(gpx_engine* h, const gpx_packed_votes* pv, int32_t* gidx, int32_t* bnum, int32_t* bcoord,
+                         int32_t* slot, int32_t* acceptor, int32_t* max_cp) {
+  int rc = packed_check(h, pv);
+  if (rc != GPX_OK) return rc;
+  if ((rc = check_batch(h, pv->n)) != GPX_OK) return rc;
+  if (pv->n == 0) return GPX_OK;
+  if (!gidx || !bnum || !bcoord || !slot || !acceptor || !max_cp) return GPX_EINVAL;
+  if (!aligned16({pv->rec, pv->exc, gidx, bnum, bcoord, slot, acceptor, max_cp})) return GPX_EINVAL;
+  LAUNCH(h, "k_votes_unpack", k_votes_unpack, grid_for(votes_unpack_lanes(pv->n)), packed_hdr(*pv),
+         (const uint4*)pv->rec, pv->exc, (int4*)gidx, (int4*)bnum, (int4*)bcoord, (int4*)slot, (int4*)acceptor,
+         (int4*)max_cp);
+  HIPCHK(hipGetLastError());
+  return GPX_OK;
+}
+
+int gpx_accept_reply_packed_dev(gpx_engine* h, const gpx_packed_votes* pv, int32_t* d_gidx, int32_t* d_slot,
+                                int32_t* d_bnum, int32_t* d_bcoord, int32_t* d_median_cp, uint8_t* d_kind,
+                                int32_t* n_out, uint8_t* status) {
+  int rc = packed_check(h, pv);
+  if (rc != GPX_OK) return rc;
+  const size_t N = packed_col_stride(h);
+  if (!h->pk_cols && (rc = dev_alloc(h, &h->pk_cols, 6 * N, false)) != GPX_OK) return rc;
+  int32_t* c = h->pk_cols;
+  if ((rc = gpx_votes_unpack_dev(h, pv, c, c + N, c + 2 * N, c + 3 * N, c + 4 * N, c + 5 * N)) != GPX_OK) return rc;
+  return gpx_accept_reply_batch_dev(h, pv->n, c, c + N, c + 2 * N, c + 3 * N, c + 4 * N, c + 5 * N, d_gidx, d_slot,
+                                    d_bnum, d_bcoord, d_median_cp, d_kind, n_out, status);
+}
+
+/* queues a packed call's inputs: 8 bytes per vote and 32 per exception row cross the link, then k_votes_unpack makes
+ * the set's six columns of them on the same stream (where the common-ballot form runs k_fill_i32) */
+static int packed_inputs(gpx_engine* h, gpx_engine::AsyncSet& a, const gpx_packed_votes* pv) {
+  hipStream_t fs = h->async_in_engine ? h->sB : h->s_in;
+  HIPCHK(xfer(h, a.pk_rec, pv->rec, (size_t)pv->n * 8, hipMemcpyHostToDevice, fs));
+  if (pv->n_exc > 0) HIPCHK(xfer(h, a.pk_exc, pv->exc, (size_t)pv->n_exc * 32, hipMemcpyHostToDevice, fs));
+  hipLaunchKernelGGL(k_votes_unpack, dim3(grid_for(votes_unpack_lanes(pv->n))), dim3(GPX_BLOCK), 0, fs, packed_hdr(*pv),
+                     (const uint4*)a.pk_rec, (const int32_t*)a.pk_exc, (int4*)a.i32[0], (int4*)a.i32[1], (int4*)a.i32[2],
+                     (int4*)a.i32[3], (int4*)a.i32[4], (int4*)a.i32[5]);
+  return GPX_OK;
+}
+
+int gpx_accept_reply_packed_async(gpx_engine* h, const gpx_packed_votes* pv, int32_t* d_gidx, int32_t* d_slot,
+                                  int32_t* d_bnum, int32_t* d_bcoord, int32_t* d_median_cp, uint8_t* d_kind,
+                                  int32_t* n_out, uint8_t* status, gpx_ticket* ticket) {
+  if (!ticket || !n_out) return GPX_EINVAL;
+  int rc = packed_check(h, pv);
+  if (rc != GPX_OK) return rc;
+  const int32_t n = pv->n;
+  if (n > 0 && (!d_gidx || !d_slot || !d_bnum || !d_bcoord || !d_median_cp || !d_kind)) return GPX_EINVAL;
+  gpx_engine::AsyncSet* ap = nullptr;
+  rc = async_begin(h, n, &ap);
+  if (rc != GPX_OK) return rc;
+  gpx_engine::AsyncSet& a = *ap;
+  const size_t N = (size_t)h->cfg.max_batch;
+  if (!a.pk_rec && (rc = dev_alloc(h, &a.pk_rec, 2 * N, false)) != GPX_OK) return rc;
+  if (!a.pk_exc && (rc = dev_alloc(h, &a.pk_exc, 8 * (N / GPX_PACKED_EXC_DIV), false)) != GPX_OK) return rc;
+  a.host_count = n_out;
+  *n_out = 0;
+  if (n > 0) {
+    if ((rc = packed_inputs(h, a, pv)) != GPX_OK) return async_fail(h, a, rc);
     if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
     h->lazy_override = 0; /* k_copy_out reads the count on the device: dense columns, always */
     rc = gpx_accept_reply_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5], a.i32[6],

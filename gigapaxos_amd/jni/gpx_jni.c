@@ -1,6 +1,6 @@
 /*
  * gpx_jni.c — the JNI shim between gigapaxos's Java host and the C-ABI of include/gpx.h /
- * include/gpx_wire.h.
+ * include/gpx_wire.h / include/gpx_packed.h.
  *
  * Compiled only where a JDK exists (none in the build image or on the GPU box: `java -version` is
  * "command not found" on both), hence the guard:
@@ -23,6 +23,7 @@
 
 #include "../../include/gpx.h"
 #include "../../include/gpx_wire.h"
+#include "../../include/gpx_packed.h"
 
 #ifdef GPX_HAVE_JNI
 #include <jni.h>
@@ -132,6 +133,19 @@ JFN(jint, acceptReplyBatchAsync)(JNIEnv* env, jclass c, jlong h, jint n, jobject
                                       B(acceptor), B(maxCp), B(dGidx), B(dSlot), B(dBnum), B(dBcoord), B(dMedian),
                                       B(dKind), B(nOut), B(status), (gpx_ticket*)B(ticket));
 }
+/* The votes as packed 8-byte records (include/gpx_packed.h): `records` holds n (gidx, w) pairs and `exceptions` nExc
+ * rows of eight ints, both written in ByteOrder.nativeOrder() while the host drains its NIO buffers; `exceptions` may be
+ * null when nExc == 0.  Both stay untouched until engineWait(ticket), like the outputs. */
+JFN(jint, acceptReplyPackedAsync)(JNIEnv* env, jclass c, jlong h, jint n, jint nExc, jint bnum, jint bcoord,
+                                  jint baseSlot, jint baseCp, jint baseAcceptor, jobject records, jobject exceptions,
+                                  jobject dGidx, jobject dSlot, jobject dBnum, jobject dBcoord, jobject dMedian,
+                                  jobject dKind, jobject nOut, jobject status, jobject ticket) {
+  (void)c;
+  const gpx_packed_votes pv = {n, nExc, bnum, bcoord, baseSlot, baseCp, baseAcceptor, 0,
+                               (const uint32_t*)B(records), (const int32_t*)B(exceptions)};
+  return gpx_accept_reply_packed_async(H(h), &pv, B(dGidx), B(dSlot), B(dBnum), B(dBcoord), B(dMedian), B(dKind),
+                                       B(nOut), B(status), (gpx_ticket*)B(ticket));
+}
 JFN(jint, acceptBatchAsync)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject bnum, jobject bcoord,
                             jobject slot, jobject medianCp, jobject aFlags, jobject rBnum, jobject rBcoord,
                             jobject rMaxCp, jobject rFlags, jobject status, jobject xGidx, jobject xFirst,
@@ -215,4 +229,7 @@ typedef int (*gpx_jni_check_ar)(gpx_engine*, int32_t, const int32_t*, const int3
                                 const int32_t*, const int32_t*, const int32_t*, int32_t*, int32_t*,
                                 int32_t*, int32_t*, int32_t*, uint8_t*, int32_t*, uint8_t*);
 static gpx_jni_check_ar gpx_jni_check_ar_ = gpx_accept_reply_batch;
-void* gpx_jni_selfcheck(void) { return (void*)gpx_jni_check_ar_; }
+typedef int (*gpx_jni_check_pk)(gpx_engine*, const gpx_packed_votes*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*,
+                                uint8_t*, int32_t*, uint8_t*, gpx_ticket*);
+static gpx_jni_check_pk gpx_jni_check_pk_ = gpx_accept_reply_packed_async;
+void* gpx_jni_selfcheck(void) { return gpx_jni_check_pk_ ? (void*)gpx_jni_check_ar_ : (void*)0; }

@@ -243,6 +243,9 @@ struct gpx_engine {
    * writes (DevScratch.xabort) */
   int cus = 0, sharers = 1;
   uint32_t xchg_test_skew = 0;          /* GPX_XCHG_TEST_SKEW (tests/test_many_engines_gpu.py): see xchg_ctl */
+  /* GPX_TEST_EPOCH_WRAP=n (tests/test_lifetime_gpu.py): X.epoch, one_epoch, small_epoch and w_epoch take their wrap
+   * branch when they reach n instead of 2^32 / 2^24 (0: unset) */
+  uint32_t test_epoch_wrap = 0;
   bool sharers_set = false;             /* GPX_DEVICE_SHARERS given: it replaces the registry of other processes */
   std::map<const void*, int> occ;       /* hipOccupancyMaxActiveBlocksPerMultiprocessor of the exchange kernels */
   uint32_t xchg_timeout_ms = GPX_XCHG_TIMEOUT_MS; /* GPX_XCHG_TIMEOUT_MS: how long an exchange kernel's pollers wait */
@@ -434,16 +437,27 @@ void apply_streams(gpx_engine* e) {
   e->sF = e->sB = e->stream = e->user_stream ? e->user_stream : e->own_stream;
 }
 
+/* GPX_TEST_EPOCH_WRAP: has this epoch counter reached the value at which a test wants its wrap branch taken? */
+inline bool epoch_wraps(const gpx_engine* e, uint32_t epoch) { return e->test_epoch_wrap && epoch >= e->test_epoch_wrap; }
+
 /* Opens a batch call: the call's epoch (what *X.unsorted is compared with). */
 int begin_front(gpx_engine* e) {
   /* whatever an earlier call left parked can no longer be compacted: gpx_compact_last_dev says so once */
   e->last.stale = e->last.kind != 0 || e->last.stale;
   e->last.kind = 0;
   e->X.epoch = (uint32_t)(e->call_seq + 1);
-  if (e->X.epoch == 0) { /* 2^32 calls: restart the epochs from cleared words */
+  if (e->X.epoch == 0 || epoch_wraps(e, e->X.epoch)) { /* 2^32 calls: restart the epochs from cleared words */
+    /* the clears go onto the engine's stream, in front of this call's kernels (the streams are non-blocking: a
+     * null-stream memset would not be ordered with them) */
     HIPQ(hipStreamSynchronize(e->stream));
-    HIPQ(hipMemset(e->fs[0].unsorted, 0, sizeof(uint32_t)));
-    HIPQ(hipMemset(e->rec_tag, 0, sizeof(uint32_t) * (size_t)e->cfg.max_batch));
+    HIPQ(hipMemsetAsync(e->fs[0].unsorted, 0, sizeof(uint32_t), e->stream));
+    HIPQ(hipMemsetAsync(e->rec_tag, 0, sizeof(uint32_t) * (size_t)e->cfg.max_batch, e->stream));
+    /* D.mark and A.ref[3] are compared with the epoch too.  Left stale, neither changed an answer in
+     * tests/test_lifetime_gpu.py (a stale mark sends a regular batch through the compaction, which goes by the tags; the
+     * staging of a tiled call is always written), but a stale A.ref[3] moves a call from "in place" to "compacted" in
+     * gpx_engine_path_counters and in the learnt ratio */
+    HIPQ(hipMemsetAsync(e->fs[0].chunk_cnt + GPX_CHUNK_CNT_MARK(e->cfg.max_batch), 0, sizeof(uint32_t), e->stream));
+    if (e->tile_area.ref) HIPQ(hipMemsetAsync(e->tile_area.ref + 3, 0, sizeof(int32_t), e->stream));
     e->X.epoch = 1;
     e->call_seq = 0;
   }
@@ -474,7 +488,7 @@ void end_call(gpx_engine* e, int) { e->call_seq++; }
 
 /* the verdict word of an ordered batch (gpx_one.hip.h) and a fresh, ascending epoch for it */
 OneCtl one_ctl(gpx_engine* e) {
-  if (++e->one_epoch == 0) { /* 2^32 launches: start the epochs again from a cleared word (the arrival counters behind it stay) */
+  if (++e->one_epoch == 0 || epoch_wraps(e, e->one_epoch)) { /* 2^32 launches: start the epochs again from a cleared word (the arrival counters behind it stay) */
     HIPQ(hipMemsetAsync(e->one_words, 0, sizeof(unsigned long long) * GPX_ONE_TICKETS, e->stream));
     e->one_epoch = 1;
   }
@@ -705,6 +719,28 @@ int gpx_engine_create(const gpx_config* cfg, gpx_engine** out) {
   if (cfg->max_groups <= 0 || cfg->kmax < 1 || cfg->kmax > GPX_KMAX_LIMIT || cfg->max_batch <= 0)
     return GPX_EINVAL;
   if (cfg->window < 4 || cfg->window > 64 || (cfg->window & (cfg->window - 1))) return GPX_EINVAL;
+  /* the two lifetime test switches: a value that cannot be meant is refused here, so that a test which sets
+   * one can tell - by setting a bad one - that this library reads the name it spelt */
+  uint32_t test_epoch_wrap = 0, test_counter_base = 0;
+  bool test_counter_base_set = false;
+  if (const char* ew = getenv("GPX_TEST_EPOCH_WRAP")) {
+    char* end = nullptr;
+    const long v = strtol(ew, &end, 10);
+    if (end == ew || *end || v < 2 || v >= (1L << 24)) {
+      snprintf(g_err, sizeof(g_err), "GPX_TEST_EPOCH_WRAP=%s: an integer in [2, 2^24) is expected", ew);
+      return GPX_EINVAL;
+    }
+    test_epoch_wrap = (uint32_t)v;
+  }
+  if (const char* cb = getenv("GPX_TEST_COUNTER_BASE")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(cb, &end, 0);
+    if (end == cb || *end || *cb == '-' || v > 0xffffffffull) {
+      snprintf(g_err, sizeof(g_err), "GPX_TEST_COUNTER_BASE=%s: an unsigned 32-bit integer is expected", cb);
+      return GPX_EINVAL;
+    }
+    test_counter_base = (uint32_t)v, test_counter_base_set = true;
+  }
   /* A GPU that has just been powered up (fresh box, "device(s) in a low-power state") can answer the
    * first runtime call with hipErrorNoDevice for a moment - seen once on the MI355X pool.  Wait for it, but
    * only where a ROCm driver is present at all (/dev/kfd): a host without a GPU fails at once. */
@@ -934,6 +970,17 @@ int gpx_engine_create(const gpx_config* cfg, gpx_engine** out) {
     if (const char* sh = getenv("GPX_DEVICE_SHARERS")) e->sharers = std::max(1, atoi(sh)), e->sharers_set = true;
     if (const char* tm = getenv("GPX_XCHG_TIMEOUT_MS")) e->xchg_timeout_ms = (uint32_t)std::max(1, atoi(tm));
     if (const char* sk = getenv("GPX_XCHG_TEST_SKEW")) e->xchg_test_skew = (uint32_t)std::max(0, atoi(sk));
+    e->test_epoch_wrap = test_epoch_wrap;
+    if (test_counter_base_set) {
+      /* test switch: the cumulative counters (grid_exchange's arrivals, k_ac_small's chunk draw) start here, on the host
+       * and on the device alike, so that a test can begin a few increments below 2^31 or 2^32 */
+      const uint32_t base = test_counter_base;
+      std::vector<uint32_t> lines((size_t)GPX_GX_LINES * 32, 0u);
+      for (int l = 0; l < GPX_GX_LINES; l++) lines[(size_t)l * 32] = base;
+      HIPCHK_CREATE(hipMemcpy(e->one_words + GPX_ONE_TICKETS, lines.data(), lines.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+      HIPCHK_CREATE(hipMemcpy(e->small_draw, &base, sizeof(base), hipMemcpyHostToDevice));
+      e->gx_arrive = e->small_drawn = base;
+    }
     if (const char* ad = getenv("GPX_ASYNC_DEPTH")) e->async_depth = std::max(1, std::min(GPX_ASYNC_DEPTH_MAX, atoi(ad)));
     HIPCHK_CREATE(hipHostMalloc((void**)&e->h_abort, 64, hipHostMallocMapped));
     memset(e->h_abort, 0, 64);
@@ -1692,7 +1739,7 @@ int gpx_accept_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const in
               e->S.G, e->X, status, D.chunk_cnt, nchunks);
   /* fused: FIRST in the stream - the partition path launched behind it reads its verdict */
   if (fused) {
-    if (++e->small_epoch == 0) {
+    if (++e->small_epoch == 0 || epoch_wraps(e, e->small_epoch)) {
       HIPQ(hipMemsetAsync(e->small_tickets, 0, 2 * (GPX_SMALL_DIRECT_MAX_N / GPX_DCHUNK) * sizeof(unsigned long long), e->stream));
       e->small_epoch = 1;
     }
@@ -1812,7 +1859,7 @@ int gpx_commit_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const in
     LAUNCH_OC(e, "k_order_check", k_order_check<false>, (n + GPX_OC_BLOCK * 8 - 1) / (GPX_OC_BLOCK * 8), 0, n, gidx,
               e->S.G, e->X, status, D.chunk_cnt, nchunks);
   if (fused) {
-    if (++e->small_epoch == 0) {
+    if (++e->small_epoch == 0 || epoch_wraps(e, e->small_epoch)) {
       HIPQ(hipMemsetAsync(e->small_tickets, 0, 2 * (GPX_SMALL_DIRECT_MAX_N / GPX_DCHUNK) * sizeof(unsigned long long), e->stream));
       e->small_epoch = 1;
     }

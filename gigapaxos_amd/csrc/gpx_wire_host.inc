@@ -464,7 +464,7 @@ int gpx_wire_decode_dev(gpx_engine* h, int32_t n_frames, const uint8_t* frames,
   {
     /* one launch: parse, place (look-back over the tiles), emit */
     const size_t nt = (size_t)(h->cfg.max_batch + GPX_BLOCK - 1) / GPX_BLOCK + 1;
-    if (++h->w_epoch >= (1u << 24)) {
+    if (++h->w_epoch >= (1u << 24) || epoch_wraps(h, h->w_epoch)) {
       HIPCHK(hipMemsetAsync(h->w_look, 0, 4 * nt * sizeof(unsigned long long), h->stream));
       h->w_epoch = 1;
     }

@@ -182,8 +182,10 @@ def cell_gmap(c):
     return hot_set(c["G"], geometry(c["G"], c["kmax"], c["shift"]), np.random.default_rng(c["seed"]), extra=300)[0]
 
 
-def run_cell(lib_a, lib_b, c, kmax=None, seed=None, ordered=False, profile=False):
-    """One fuzz cell: engine a against engine b.  Returns (statuses seen per operation, kernels engine a launched)."""
+def run_cell(lib_a, lib_b, c, kmax=None, seed=None, ordered=False, profile=False, steps=None, counted=None):
+    """One fuzz cell: engine a against engine b.  Returns (statuses seen per operation, kernels engine a launched).
+    steps: another number of fuzz steps than the cell's own.  counted: a wrapper class for engine a that counts its
+    calls (tests/lifetime_common.py: Counted); the answer is then (statuses, the wrapper, {kernel: launches})."""
     from tests.parity_common import make_pair, create_mixed_groups, fuzz
     kmax = c["kmax"] if kmax is None else kmax
     seed = c["seed"] if seed is None else seed
@@ -194,11 +196,15 @@ def run_cell(lib_a, lib_b, c, kmax=None, seed=None, ordered=False, profile=False
     H = G if gmap is None else gmap.shape[0]
     ea, eb = make_pair(lib_a, lib_b, 100, G, kmax, c["window"], max_batch=c.get("max_batch", 1 << 16))
     create_mixed_groups(ea, eb, H, kmax, nodes, rng, gmap=gmap)
+    profile = profile and "profile_enable" in ea.lib.fn   # (the oracle has no kernels to name)
     if profile:
         ea.profile(2)
-    seen = fuzz(ea, eb, H, nodes, rng, steps=c["steps"], batch=c["batch"], min_batch=c.get("min_batch", 1),
-                gmap=gmap, ordered=ordered, span=c.get("span", FUZZ_SPAN))
-    ran = set(ea.profile_read()) if profile else set()
+    ef = ea if counted is None else counted(ea)
+    seen = fuzz(ef, eb, H, nodes, rng, steps=c["steps"] if steps is None else steps, batch=c["batch"],
+                min_batch=c.get("min_batch", 1), gmap=gmap, ordered=ordered, span=c.get("span", FUZZ_SPAN))
+    prof = ea.profile_read() if profile else {}
     ea.close()
     eb.close()
-    return seen, ran
+    if counted is not None:
+        return seen, ef, {k: v[0] for k, v in prof.items()}
+    return seen, set(prof)

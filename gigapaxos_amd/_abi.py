@@ -55,6 +55,11 @@ class GpxKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
 
+class GpxPackedOutHdr(C.Structure):
+    """struct gpx_packed_out_hdr (include/gpx_packed_out.h): the first 32 bytes of a packed output buffer."""
+    _fields_ = [(f, C.c_int32) for f in ("form", "kind", "n", "n_exc", "bnum", "bcoord", "base_slot", "base_cp")]
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -138,6 +143,11 @@ _DEV_SIGS = {
     "votes_unpack_dev": [C.POINTER(GpxPackedVotes)] + [_VP] * 6,
     "accept_reply_packed_dev": [C.POINTER(GpxPackedVotes)] + [_VP] * 8,
     "accept_reply_packed_async": [C.POINTER(GpxPackedVotes)] + [_VP] * 8 + [C.POINTER(C.c_uint64)],
+    # packed outputs (include/gpx_packed_out.h)
+    "decisions_pack_dev": [_VP, C.c_int32] + [_VP] * 7,
+    "proposals_pack_dev": [C.c_int32] + [_VP] * 6,
+    "propose_packed_out_async": [C.c_int32, _VP, _VP, _VP, C.c_size_t, C.POINTER(C.c_uint64)],
+    "accept_reply_packed_io_async": [C.POINTER(GpxPackedVotes), _VP, C.c_size_t, _VP, C.POINTER(C.c_uint64)],
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],
@@ -147,7 +157,14 @@ _DEV_SIGS = {
 _HOST_SIGS = {
     "votes_pack": [C.c_int32] + [_VP] * 8 + [C.c_int32, C.POINTER(GpxPackedVotes)],
     "votes_unpack": [C.POINTER(GpxPackedVotes)] + [_VP] * 6,
+    # include/gpx_packed_out.h
+    "packed_out_size": [_VP],
+    "decisions_pack": [C.c_int32] + [_VP] * 7 + [C.c_size_t],
+    "proposals_pack": [C.c_int32] + [_VP] * 6 + [C.c_size_t],
+    "decisions_unpack": [_VP, C.c_size_t, C.c_int32] + [_VP] * 7,
+    "proposals_unpack": [_VP, C.c_size_t, C.c_int32] + [_VP] * 6,
 }
+_HOST_RESTYPES = {"packed_out_size": C.c_int64}  # every other function returns int
 
 EXPORTED_SYMBOLS = (
     ["abi_version", "last_error", "engine_create"] + list(_SIGS) + list(_DEV_SIGS) + list(_HOST_SIGS)
@@ -200,7 +217,7 @@ class GpxLib:
         for name, args in (_HOST_SIGS if device_api else {}).items():
             f = getattr(self.lib, prefix + name)
             f.argtypes = args
-            f.restype = C.c_int
+            f.restype = _HOST_RESTYPES.get(name, C.c_int)
             self.fn[name] = f
         self.device_api = device_api
 
@@ -618,6 +635,75 @@ class Engine:
         pv = header.struct(rec_ptr, exc_ptr)
         args = [_VP(int(p)) if p else None for p in out_ptrs]
         self.lib.check(self.lib.fn["accept_reply_packed_dev"](self.h, C.byref(pv), *args), "accept_reply_packed_dev")
+
+    # -- packed outputs (include/gpx_packed_out.h) ------------------------------------------------------
+    def _packed_out_buffer(self, n, out):
+        from .packed_out import packed_out_bytes
+        need = packed_out_bytes(n)
+        if out is None:
+            out = np.zeros(need, np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+            raise ValueError("out: a contiguous uint8 array")
+        return out
+
+    def propose_packed_out_async(self, gidx, is_stop=None, out=None):
+        """gpx_propose_packed_out_async: propose_async with the five output columns coming back as ONE packed buffer
+        (4 bytes per proposal in the steady state instead of 17).  `out` is a uint8 array of at least
+        packed_out.packed_out_bytes(n) bytes (pageable, registered or from host_alloc; default: a fresh pageable one).
+        wait() returns what propose_async's returns - unpacked on the host - and leaves the raw buffer in the Pending's
+        `raw` and its view in `packed`."""
+        from .packed_out import PackedOut, unpack_proposals
+        gidx = _i32(gidx)
+        n = gidx.shape[0]
+        is_stop = _u8(is_stop, n)
+        out = self._packed_out_buffer(n, out)
+        t = C.c_uint64(0)
+        self.lib.check(self.lib.fn["propose_packed_out_async"](self.h, n, _p(gidx), _p(is_stop), _p(out), out.nbytes,
+                                                               C.byref(t)), "propose_packed_out_async")
+        pend = Engine.Pending(self, t.value, (gidx, is_stop, out), None)
+        pend.raw = out
+
+        def finish():
+            pend.packed = PackedOut(out)
+            return unpack_proposals(out, lib=self.lib)
+        pend.finish = finish
+        return pend
+
+    def accept_reply_packed_io_async(self, packed, out=None, want_status=True, status=None):
+        """gpx_accept_reply_packed_io_async: packed votes in (a packed.PackedVotes over host arrays), packed decisions out
+        (`out` as for propose_packed_out_async, for packed.n entries).  The per-vote status stays a plain byte column
+        (`status`: an array to fill; want_status=False: none).  wait() returns the Decisions accept_reply_async's returns."""
+        from .packed_out import PackedOut, unpack_decisions
+        n = packed.n
+        out = self._packed_out_buffer(n, out)
+        if status is None and want_status:
+            status = np.zeros(n, np.uint8)
+        t = C.c_uint64(0)
+        pv = packed.struct()
+        self.lib.check(self.lib.fn["accept_reply_packed_io_async"](self.h, C.byref(pv), _p(out), out.nbytes, _p(status),
+                                                                   C.byref(t)), "accept_reply_packed_io_async")
+        pend = Engine.Pending(self, t.value, (packed, out, status), None)
+        pend.raw = out
+
+        def finish():
+            pend.packed = PackedOut(out)
+            dg, ds, db, dc, dm, dk = unpack_decisions(out, lib=self.lib)
+            return Decisions(dg, ds, db, dc, dm, dk, status)
+        pend.finish = finish
+        return pend
+
+    def decisions_pack_dev(self, n_out_ptr: int, cap: int, col_ptrs, out_ptr: int):
+        """gpx_decisions_pack_dev: n_out_ptr, the six col_ptrs (d_gidx, d_slot, d_bnum, d_bcoord, d_median_cp, d_kind) and
+        out_ptr are integer device addresses, 16-byte aligned; the entry count is read on the device."""
+        args = [_VP(int(p)) if p else None for p in col_ptrs]
+        self.lib.check(self.lib.fn["decisions_pack_dev"](self.h, _VP(int(n_out_ptr) or None), int(cap), *args,
+                                                         _VP(int(out_ptr) or None)), "decisions_pack_dev")
+
+    def proposals_pack_dev(self, n: int, col_ptrs, out_ptr: int):
+        """gpx_proposals_pack_dev: col_ptrs = slot, bnum, bcoord, median_cp, status as integer device addresses."""
+        args = [_VP(int(p)) if p else None for p in col_ptrs]
+        self.lib.check(self.lib.fn["proposals_pack_dev"](self.h, int(n), *args, _VP(int(out_ptr) or None)),
+                       "proposals_pack_dev")
 
     def accept_async(self, gidx, bnum, bcoord, slot, median_cp, a_flags=None):
         gidx = _i32(gidx)

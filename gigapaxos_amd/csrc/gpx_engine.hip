@@ -37,6 +37,7 @@
 #include "gpx_wire_accept.hip.h"
 #include "gpx_elect.hip.h"
 #include "gpx_packed.hip.h"
+#include "gpx_packed_out.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -301,6 +302,12 @@ struct gpx_engine {
      * land before k_votes_unpack makes i32[0..5] of them (first packed call) */
     uint32_t* pk_rec = nullptr;
     int32_t* pk_exc = nullptr;
+    /* the packed-output calls (include/gpx_packed_out.h): where the pack kernels leave the call's buffer,
+     * GPX_PACKED_OUT_BYTES(max_batch) bytes (first such call); and, when the caller's buffer is not written through a
+     * mapping, that buffer: gpx_engine_wait fetches the header (into h_cnt), then exactly the bytes it names */
+    uint8_t* po_stage = nullptr;
+    void* po_host = nullptr;
+    size_t po_bytes = 0;
   } as[GPX_ASYNC_DEPTH_MAX];
   int async_depth = GPX_ASYNC_DEPTH; /* sets in use (GPX_ASYNC_DEPTH=n, up to GPX_ASYNC_DEPTH_MAX) */
   hipStream_t s_in = nullptr;
@@ -328,6 +335,7 @@ struct gpx_engine {
   int32_t* w_ones = nullptr;       /* a column of ones (gpx_request_batch without weights) */
   AccScratch wa{};                 /* ACCEPT packing (gpx_wire_pack_accepts_dev), rec == nullptr until first use */
   int32_t* pk_cols = nullptr;      /* gpx_accept_reply_packed_dev: six unpacked columns, 16-byte aligned (first use) */
+  int32_t* po_counts = nullptr;    /* the pack kernels' rows per workgroup, [max_batch / GPX_PO_QUAD + 1] (first use) */
 };
 
 namespace {
@@ -2525,6 +2533,7 @@ int async_begin(gpx_engine* e, int32_t n, gpx_engine::AsyncSet** out) {
   a.host_kind = nullptr;
   a.dev_kind = nullptr;
   a.host_count = nullptr;
+  a.po_host = nullptr;
   a.h_cnt[0] = 0;
   *out = &a;
   return GPX_OK;
@@ -2630,6 +2639,45 @@ int async_submit(gpx_engine* e, gpx_engine::AsyncSet& a, bool with_count, gpx_ti
   return GPX_OK;
 }
 #define A_OUT(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyDeviceToHost, a.s_out))
+
+/* ---- packed outputs (include/gpx_packed_out.h) ---- */
+/* the two pack launches over up to `cap` entries of S on the engine's stream; n_dev = the device count, or null for cap */
+template <int KIND>
+int po_pack(gpx_engine* h, const int32_t* n_dev, int32_t cap, const PoSrc& S, void* out_dev) {
+  int rc = GPX_OK;
+  if (!h->po_counts && (rc = dev_alloc(h, &h->po_counts, (size_t)h->cfg.max_batch / GPX_PO_QUAD + 1, false)) != GPX_OK)
+    return rc;
+  h->stream = h->sB;
+  const int grid = po_grid(cap);
+  LAUNCH(h, "k_po_count", k_po_count<KIND>, grid, n_dev, cap, S, h->po_counts, (int4*)out_dev);
+  LAUNCH(h, "k_po_write", k_po_write<KIND>, grid, n_dev, cap, S, (const int32_t*)h->po_counts, (uint8_t*)out_dev);
+  HIPCHK(hipGetLastError());
+  return GPX_OK;
+}
+/* the set's staging area for a packed buffer */
+int po_stage(gpx_engine* e, gpx_engine::AsyncSet& a) {
+  if (a.po_stage) return GPX_OK;
+  return dev_alloc(e, &a.po_stage, GPX_PACKED_OUT_BYTES(e->cfg.max_batch), false);
+}
+/* an empty call's buffer: the header alone, written at once */
+void po_empty(void* out, int32_t kind) {
+  const gpx_packed_out_hdr H{GPX_PO_RECORDS, kind, 0, 0, 0, 0, 0, 0};
+  memcpy(out, &H, sizeof(H));
+}
+/* the staged buffer of a call over n entries to the caller: through the mapping of a block the engine knows to be pinned
+ * (the length is read on the device), else left to gpx_engine_wait, which needs the header first */
+int po_out(gpx_engine* e, gpx_engine::AsyncSet& a, void* out, size_t out_bytes, int32_t n) {
+  void* d = (e->async_no_direct || ((uintptr_t)out & 15)) ? nullptr : mapped_host(e, out, GPX_PACKED_OUT_BYTES(n));
+  if (d && !((uintptr_t)d & 15)) {
+    hipLaunchKernelGGL(k_po_copy_out, dim3(512), dim3(256), 0, a.s_out, (const uint4*)a.po_stage, (uint4*)d,
+                       (int64_t)GPX_PACKED_OUT_BYTES(n));
+    return GPX_OK;
+  }
+  HIPCHK(hipMemcpyAsync(a.h_cnt, a.po_stage, sizeof(gpx_packed_out_hdr), hipMemcpyDeviceToHost, a.s_out));
+  a.po_host = out;
+  a.po_bytes = out_bytes;
+  return GPX_OK;
+}
 
 }  // namespace
 
@@ -2862,6 +2910,95 @@ int gpx_accept_reply_packed_async(gpx_engine* h, const gpx_packed_votes* pv, int
   return rc == GPX_OK ? rc : async_fail(h, a, rc);
 }
 
+/* ---- packed outputs (include/gpx_packed_out.h) ---- */
+int gpx_decisions_pack_dev(gpx_engine* h, const int32_t* n_out_dev, int32_t cap, const int32_t* d_gidx,
+                           const int32_t* d_slot, const int32_t* d_bnum, const int32_t* d_bcoord,
+                           const int32_t* d_median_cp, const uint8_t* d_kind, void* out_dev) {
+  int rc = check_batch(h, cap);
+  if (rc != GPX_OK) return rc;
+  if (!n_out_dev || !out_dev || ((uintptr_t)n_out_dev & 3)) return GPX_EINVAL;
+  if (cap > 0 && (!d_gidx || !d_slot || !d_bnum || !d_bcoord || !d_median_cp || !d_kind)) return GPX_EINVAL;
+  if (!aligned16({out_dev, d_gidx, d_slot, d_bnum, d_bcoord, d_median_cp, d_kind})) return GPX_EINVAL;
+  return po_pack<GPX_PO_DECISIONS>(h, n_out_dev, cap, PoSrc{d_gidx, d_slot, d_bnum, d_bcoord, d_median_cp, d_kind}, out_dev);
+}
+
+int gpx_proposals_pack_dev(gpx_engine* h, int32_t n, const int32_t* slot, const int32_t* bnum, const int32_t* bcoord,
+                           const int32_t* median_cp, const uint8_t* status, void* out_dev) {
+  int rc = check_batch(h, n);
+  if (rc != GPX_OK) return rc;
+  if (!out_dev || (n > 0 && (!slot || !bnum || !bcoord || !median_cp || !status))) return GPX_EINVAL;
+  if (!aligned16({out_dev, slot, bnum, bcoord, median_cp, status})) return GPX_EINVAL;
+  return po_pack<GPX_PO_PROPOSALS>(h, nullptr, n, PoSrc{nullptr, slot, bnum, bcoord, median_cp, status}, out_dev);
+}
+
+int gpx_propose_packed_out_async(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop, void* out,
+                                 size_t out_bytes, gpx_ticket* ticket) {
+  if (!h || !ticket || !out || (n > 0 && !gidx)) return GPX_EINVAL;
+  int rc = check_batch(h, n);
+  if (rc != GPX_OK) return rc;
+  if (out_bytes < GPX_PACKED_OUT_BYTES(n)) return GPX_ECAPACITY;
+  gpx_engine::AsyncSet* ap = nullptr;
+  if ((rc = async_begin(h, n, &ap)) != GPX_OK) return rc;
+  gpx_engine::AsyncSet& a = *ap;
+  if ((rc = po_stage(h, a)) != GPX_OK) return rc;
+  if (n > 0) {
+    {
+      const int32_t* hs[1] = {gidx};
+      int32_t* dd[1] = {a.i32[0]};
+      if ((rc = async_inputs(h, n, 1, hs, dd, is_stop, a.u8[0])) != GPX_OK) return async_fail(h, a, rc);
+    }
+    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
+    rc = propose_dev_impl(h, n, a.i32[0], is_stop ? a.u8[0] : nullptr, nullptr, a.i32[1], a.i32[2], a.i32[3],
+                          a.i32[4], a.u8[1]);
+    if (rc == GPX_OK) rc = gpx_proposals_pack_dev(h, n, a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.u8[1], a.po_stage);
+    if (rc != GPX_OK) return async_fail(h, a, rc);
+    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
+    if ((rc = po_out(h, a, out, out_bytes, n)) != GPX_OK) return async_fail(h, a, rc);
+  } else {
+    po_empty(out, GPX_PO_PROPOSALS);
+  }
+  rc = async_submit(h, a, false, ticket);
+  return rc == GPX_OK ? rc : async_fail(h, a, rc);
+}
+
+int gpx_accept_reply_packed_io_async(gpx_engine* h, const gpx_packed_votes* pv, void* out, size_t out_bytes,
+                                     uint8_t* status, gpx_ticket* ticket) {
+  if (!ticket || !out) return GPX_EINVAL;
+  int rc = packed_check(h, pv);
+  if (rc != GPX_OK) return rc;
+  const int32_t n = pv->n;
+  if (out_bytes < GPX_PACKED_OUT_BYTES(n)) return GPX_ECAPACITY;
+  gpx_engine::AsyncSet* ap = nullptr;
+  if ((rc = async_begin(h, n, &ap)) != GPX_OK) return rc;
+  gpx_engine::AsyncSet& a = *ap;
+  const size_t N = (size_t)h->cfg.max_batch;
+  if (!a.pk_rec && (rc = dev_alloc(h, &a.pk_rec, 2 * N, false)) != GPX_OK) return rc;
+  if (!a.pk_exc && (rc = dev_alloc(h, &a.pk_exc, 8 * (N / GPX_PACKED_EXC_DIV), false)) != GPX_OK) return rc;
+  if ((rc = po_stage(h, a)) != GPX_OK) return rc;
+  if (n > 0) {
+    if ((rc = packed_inputs(h, a, pv)) != GPX_OK) return async_fail(h, a, rc);
+    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
+    h->lazy_override = 0; /* the pack kernels read the count on the device: dense columns, always */
+    rc = gpx_accept_reply_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5], a.i32[6],
+                                    a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.cnt, a.u8[1]);
+    h->lazy_override = -1;
+    if (rc == GPX_OK)
+      rc = gpx_decisions_pack_dev(h, a.cnt, n, a.i32[6], a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.po_stage);
+    if (rc != GPX_OK) return async_fail(h, a, rc);
+    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
+    if (status) {
+      uint8_t* hb[1] = {status};
+      const uint8_t* db[1] = {a.u8[1]};
+      if ((rc = async_dense_out(h, a, n, 0, nullptr, nullptr, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
+    }
+    if ((rc = po_out(h, a, out, out_bytes, n)) != GPX_OK) return async_fail(h, a, rc);
+  } else {
+    po_empty(out, GPX_PO_DECISIONS);
+  }
+  rc = async_submit(h, a, false, ticket);
+  return rc == GPX_OK ? rc : async_fail(h, a, rc);
+}
+
 int gpx_commit_batch_async(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
                            const int32_t* bcoord, const int32_t* slot, const int32_t* median_cp,
                            const uint8_t* c_kind, uint8_t* status, int32_t* x_gidx, int32_t* x_first,
@@ -2909,6 +3046,18 @@ int gpx_engine_wait(gpx_engine* h, gpx_ticket ticket) {
     if (int rc_abort = check_batch(h, 0)) { /* an exchange kernel of this call (or one before it) gave up: nothing to hand over */
       a.busy = false;
       return rc_abort;
+    }
+    if (a.po_host) { /* a packed buffer outside mapped memory: the header is here, it says how much there is to fetch */
+      void* dst = a.po_host;
+      a.po_host = nullptr;
+      const int64_t used = po_size(a.h_cnt[0], a.h_cnt[1], a.h_cnt[2], a.h_cnt[3]);
+      if (used < 32 || (uint64_t)used > a.po_bytes) {
+        a.busy = false;
+        snprintf(g_err, sizeof(g_err), "packed output header names %lld bytes for a buffer of %zu", (long long)used, a.po_bytes);
+        return GPX_EDEVICE;
+      }
+      A_OUT(dst, a.po_stage, (size_t)used);
+      SYNC_CHECKED(h, a.s_out);
     }
     if (a.host_count && !a.direct) {
       const int32_t m = a.ncols ? a.h_cnt[0] : 0;

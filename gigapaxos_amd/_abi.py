@@ -541,24 +541,58 @@ class Engine:
         mm = mmap.mmap(-1, (nbytes + mmap.PAGESIZE - 1) // mmap.PAGESIZE * mmap.PAGESIZE)
         return np.frombuffer(mm, dtype=dt, count=int(n))
 
+    def _async_call(self, name, shapes, pin_outputs, submit, keep, result):
+        """One asynchronous call.  Allocates its output arrays - `shapes`: (entries, dtype) each; pageable, or with
+        pin_outputs whole pages of their own, registered (gpx_host_register) for the length of the call: the engine then
+        writes them itself, without a host round trip for the count - and submits it: submit(outs, ticket) -> rc.
+        wait() unregisters the outputs and returns result(*outs); a refused call leaves no registration behind."""
+        mk = Engine.page_array if pin_outputs else np.zeros
+        outs = tuple(mk(max(c, 1), dt) for c, dt in shapes)
+        if pin_outputs:
+            self.host_register(*outs)
+
+        def release():
+            if pin_outputs:
+                self.host_unregister(*outs)
+        t = C.c_uint64(0)
+        try:
+            self.lib.check(submit(outs, C.byref(t)), name)
+        except GpxError:
+            release()
+            raise
+
+        def finish():
+            release()
+            return result(*outs)
+        return Engine.Pending(self, t.value, keep, finish)
+
+    @staticmethod
+    def _decision_outputs(n):
+        """Output shapes and result of the accept-reply calls: five compacted columns, their kinds, the count, the status."""
+        def result(dg, ds, db, dc, dm, dk, no, status):
+            m = int(no[0])
+            return Decisions(dg[:m], ds[:m], db[:m], dc[:m], dm[:m], dk[:m], status[:n])
+        return [(n, np.int32)] * 5 + [(n, np.uint8), (1, np.int32), (n, np.uint8)], result
+
+    @staticmethod
+    def _run_outputs(n, dense, single=False):
+        """Output shapes and result of accept / commit: per-record columns of the `dense` dtypes (returned as a tuple, or
+        the one column alone when `single`), three compacted ones, the count."""
+        def result(*outs):
+            m = int(outs[-1][0])
+            per_record = tuple(o[:n] for o in outs[:len(dense)])
+            return per_record[0] if single else per_record, ExecRuns(*(x[:m] for x in outs[len(dense):-1]))
+        return [(n, dt) for dt in dense] + [(n, np.int32)] * 3 + [(1, np.int32)], result
+
     def propose_async(self, gidx, is_stop=None, pin_outputs=False):
         gidx = _i32(gidx)
         n = gidx.shape[0]
         is_stop = _u8(is_stop, n)
-        mk = Engine.page_array if pin_outputs else np.zeros   # registered outputs: whole pages of their own
-        slot, bnum, bcoord, median = (mk(n, np.int32) for _ in range(4))
-        status = mk(n, np.uint8)
-        outs = (slot, bnum, bcoord, median, status)
-        if pin_outputs:
-            self.host_register(*outs)
-        t = C.c_uint64(0)
-        self.lib.check(self.lib.fn["propose_batch_async"](self.h, n, _p(gidx), _p(is_stop), _p(slot), _p(bnum), _p(bcoord),
-                                                          _p(median), _p(status), C.byref(t)), "propose_batch_async")
-        def finish():
-            if pin_outputs:
-                self.host_unregister(*outs)
-            return slot, bnum, bcoord, median, status
-        return Engine.Pending(self, t.value, (gidx, is_stop), finish)
+        fn = self.lib.fn["propose_batch_async"]
+        return self._async_call(
+            "propose_batch_async", [(n, np.int32)] * 4 + [(n, np.uint8)], pin_outputs,
+            lambda o, t: fn(self.h, n, _p(gidx), _p(is_stop), *map(_p, o), t),
+            (gidx, is_stop), lambda *o: tuple(x[:n] for x in o))
 
     def accept_reply_async(self, gidx, bnum, bcoord, slot, acceptor, max_cp, common_ballot=None, pin_outputs=False):
         """bnum / bcoord None + common_ballot = (bnum, bcoord): every vote carries that ballot.
@@ -570,57 +604,22 @@ class Engine:
         if bnum is not None:
             bnum, bcoord = _i32(bnum, n), _i32(bcoord, n)
         cb = common_ballot or (0, 0)
-        cap = max(n, 1)
-        mk = Engine.page_array if pin_outputs else np.zeros   # registered outputs: whole pages of their own
-        dg, ds, db, dc, dm = (mk(cap, np.int32) for _ in range(5))
-        dk = mk(cap, np.uint8)
-        status = mk(n, np.uint8)
-        no = mk(1, np.int32)
-        outs = (dg, ds, db, dc, dm, dk, no, status)
-        if pin_outputs:
-            self.host_register(*outs)
-        t = C.c_uint64(0)
-        self.lib.check(self.lib.fn["accept_reply_batch_async"](
-            self.h, n, _p(gidx), _p(bnum), _p(bcoord), int(cb[0]), int(cb[1]), _p(slot), _p(acceptor), _p(max_cp),
-            _p(dg), _p(ds), _p(db), _p(dc), _p(dm), _p(dk), _p(no), _p(status), C.byref(t)), "accept_reply_batch_async")
-
-        def finish():
-            if pin_outputs:
-                self.host_unregister(*outs)
-            m = int(no[0])
-            return Decisions(dg[:m], ds[:m], db[:m], dc[:m], dm[:m], dk[:m], status)
-        return Engine.Pending(self, t.value, (gidx, bnum, bcoord, slot, acceptor, max_cp), finish)
+        shapes, result = Engine._decision_outputs(n)
+        fn = self.lib.fn["accept_reply_batch_async"]
+        return self._async_call(
+            "accept_reply_batch_async", shapes, pin_outputs,
+            lambda o, t: fn(self.h, n, _p(gidx), _p(bnum), _p(bcoord), int(cb[0]), int(cb[1]), _p(slot), _p(acceptor),
+                            _p(max_cp), *map(_p, o), t),
+            (gidx, bnum, bcoord, slot, acceptor, max_cp), result)
 
     def accept_reply_packed_async(self, packed, pin_outputs=False):
         """gpx_accept_reply_packed_async: `packed` is a packed.PackedVotes over host arrays (its records and exception
         rows cross the link instead of the columns).  Outputs as accept_reply_async."""
-        n = packed.n
-        cap = max(n, 1)
-        mk = Engine.page_array if pin_outputs else np.zeros   # registered outputs: whole pages of their own
-        dg, ds, db, dc, dm = (mk(cap, np.int32) for _ in range(5))
-        dk = mk(cap, np.uint8)
-        status = mk(n, np.uint8)
-        no = mk(1, np.int32)
-        outs = (dg, ds, db, dc, dm, dk, no, status)
-        if pin_outputs:
-            self.host_register(*outs)
-        t = C.c_uint64(0)
+        shapes, result = Engine._decision_outputs(packed.n)
+        fn = self.lib.fn["accept_reply_packed_async"]
         pv = packed.struct()
-        try:
-            self.lib.check(self.lib.fn["accept_reply_packed_async"](
-                self.h, C.byref(pv), _p(dg), _p(ds), _p(db), _p(dc), _p(dm), _p(dk), _p(no), _p(status), C.byref(t)),
-                "accept_reply_packed_async")
-        except GpxError:
-            if pin_outputs:
-                self.host_unregister(*outs)
-            raise
-
-        def finish():
-            if pin_outputs:
-                self.host_unregister(*outs)
-            m = int(no[0])
-            return Decisions(dg[:m], ds[:m], db[:m], dc[:m], dm[:m], dk[:m], status)
-        return Engine.Pending(self, t.value, (packed,), finish)
+        return self._async_call("accept_reply_packed_async", shapes, pin_outputs,
+                                lambda o, t: fn(self.h, C.byref(pv), *map(_p, o), t), (packed, pv), result)
 
     def votes_unpack_dev(self, header, rec_ptr: int, exc_ptr: int, col_ptrs):
         """gpx_votes_unpack_dev: `header` is a packed.PackedVotes (its fields go by value), rec_ptr / exc_ptr and the six
@@ -705,42 +704,29 @@ class Engine:
         self.lib.check(self.lib.fn["proposals_pack_dev"](self.h, int(n), *args, _VP(int(out_ptr) or None)),
                        "proposals_pack_dev")
 
-    def accept_async(self, gidx, bnum, bcoord, slot, median_cp, a_flags=None):
+    def accept_async(self, gidx, bnum, bcoord, slot, median_cp, a_flags=None, pin_outputs=False):
         gidx = _i32(gidx)
         n = gidx.shape[0]
         bnum, bcoord, slot, median_cp = (_i32(x, n) for x in (bnum, bcoord, slot, median_cp))
         a_flags = _u8(a_flags, n)
-        r_bnum, r_bcoord, r_maxcp = (np.zeros(n, np.int32) for _ in range(3))
-        r_flags, status = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
-        xg, xf, xc = (np.zeros(max(n, 1), np.int32) for _ in range(3))
-        nr = np.zeros(1, np.int32)
-        t = C.c_uint64(0)
-        self.lib.check(self.lib.fn["accept_batch_async"](
-            self.h, n, _p(gidx), _p(bnum), _p(bcoord), _p(slot), _p(median_cp), _p(a_flags), _p(r_bnum), _p(r_bcoord),
-            _p(r_maxcp), _p(r_flags), _p(status), _p(xg), _p(xf), _p(xc), _p(nr), C.byref(t)), "accept_batch_async")
+        shapes, result = Engine._run_outputs(n, [np.int32] * 3 + [np.uint8] * 2)
+        fn = self.lib.fn["accept_batch_async"]
+        return self._async_call(
+            "accept_batch_async", shapes, pin_outputs,
+            lambda o, t: fn(self.h, n, _p(gidx), _p(bnum), _p(bcoord), _p(slot), _p(median_cp), _p(a_flags), *map(_p, o), t),
+            (gidx, bnum, bcoord, slot, median_cp, a_flags), result)
 
-        def finish():
-            m = int(nr[0])
-            return (r_bnum, r_bcoord, r_maxcp, r_flags, status), ExecRuns(xg[:m], xf[:m], xc[:m])
-        return Engine.Pending(self, t.value, (gidx, bnum, bcoord, slot, median_cp, a_flags), finish)
-
-    def commit_async(self, gidx, bnum, bcoord, slot, median_cp, c_kind=None):
+    def commit_async(self, gidx, bnum, bcoord, slot, median_cp, c_kind=None, pin_outputs=False):
         gidx = _i32(gidx)
         n = gidx.shape[0]
         bnum, bcoord, slot, median_cp = (_i32(x, n) for x in (bnum, bcoord, slot, median_cp))
         c_kind = _u8(c_kind, n)
-        status = np.zeros(n, np.uint8)
-        xg, xf, xc = (np.zeros(max(n, 1), np.int32) for _ in range(3))
-        nr = np.zeros(1, np.int32)
-        t = C.c_uint64(0)
-        self.lib.check(self.lib.fn["commit_batch_async"](
-            self.h, n, _p(gidx), _p(bnum), _p(bcoord), _p(slot), _p(median_cp), _p(c_kind), _p(status), _p(xg), _p(xf),
-            _p(xc), _p(nr), C.byref(t)), "commit_batch_async")
-
-        def finish():
-            m = int(nr[0])
-            return status, ExecRuns(xg[:m], xf[:m], xc[:m])
-        return Engine.Pending(self, t.value, (gidx, bnum, bcoord, slot, median_cp, c_kind), finish)
+        shapes, result = Engine._run_outputs(n, [np.uint8], single=True)
+        fn = self.lib.fn["commit_batch_async"]
+        return self._async_call(
+            "commit_batch_async", shapes, pin_outputs,
+            lambda o, t: fn(self.h, n, _p(gidx), _p(bnum), _p(bcoord), _p(slot), _p(median_cp), _p(c_kind), *map(_p, o), t),
+            (gidx, bnum, bcoord, slot, median_cp, c_kind), result)
 
     # -- data path ---------------------------------------------------------------
     def propose(self, gidx, is_stop=None, handle=None):

@@ -238,7 +238,7 @@ struct gpx_engine {
     uint64_t seq = 0; /* call_seq right after the call: gpx_compact_last_dev refuses once another batch call came in between */
     bool stale = false; /* a pending compaction was overtaken by another batch call (begin_front) */
   } last;
-  int lazy_override = -1; /* 1: the host-pointer twins compact on demand themselves; 0: asynchronous calls need dense columns */
+  int lazy_override = -1; /* set for the length of a twin call by the host-pointer drivers alone (LazyScope, gpx_host_calls.inc) */
   /* one-launch calls (gpx_one.hip.h: judges that meet at arrival counters): the device's CUs and the processes sharing
    * it (GPX_DEVICE_SHARERS, default 1) decide which grids need no tickets; the host-mapped word a waiter that gave up
    * writes (DevScratch.xabort) */
@@ -316,9 +316,7 @@ struct gpx_engine {
    * drain before gpx_host_unregister, and what gpx_engine_destroy still has to unregister */
   std::vector<std::pair<char*, size_t>> registered;
   std::map<char*, bool> registered_own; /* block -> pinned by this engine (false: it was pinned already; not ours to unpin) */
-  bool async_in_engine = false, async_fill_memset = false; /* experiments: GPX_ASYNC_IN, GPX_ASYNC_FILL */
   bool async_no_direct = false; /* GPX_ASYNC_DIRECT=0: compacted outputs fetched by gpx_engine_wait even from registered memory */
-  bool async_kernel_in = false; /* GPX_ASYNC_COPYIN=kernel (experiment): inputs read by k_copy_in from registered memory */
   /* wire codec (gpx_wire_host.inc): paxosID table, row free list, scratch - allocated on first use */
   DevNames N{};
   int64_t nm_tomb = 0;
@@ -2066,324 +2064,15 @@ int gpx_propose_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const u
   return propose_dev_impl(h, n, gidx, is_stop, nullptr, slot, bnum, bcoord, median_cp, status);
 }
 
+} /* extern "C" */
+
 /* ---- host-pointer data path ---------------------------------------------------- */
-/* H2D into the engine's staging columns, the _dev twin, D2H of the results.        */
+/* H2D into device columns, the _dev twin, D2H of the results: gpx_host_calls.inc, included below */
 
 #define H2D(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyHostToDevice, h->sF))
 /* lifecycle calls change group state: everything on the back-end stream, in call order */
 #define H2D_B(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyHostToDevice, h->sB))
 #define D2H(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyDeviceToHost, h->sB))
-
-int gpx_propose_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop,
-                      int32_t* slot, int32_t* bnum, int32_t* bcoord, int32_t* median_cp,
-                      uint8_t* status) {
-  return gpx_propose_batch_h(h, n, gidx, is_stop, nullptr, slot, bnum, bcoord, median_cp, status);
-}
-
-int gpx_propose_batch_h(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop,
-                        const int64_t* handle, int32_t* slot, int32_t* bnum, int32_t* bcoord,
-                        int32_t* median_cp, uint8_t* status) {
-  int rc = check_batch(h, n);
-  if (rc != GPX_OK) return rc;
-  if (n == 0) return GPX_OK;
-  if (!gidx || !slot || !bnum || !bcoord || !median_cp || !status) return GPX_EINVAL;
-  const size_t b4 = (size_t)n * 4;
-  if (n <= GPX_STAGE_N) { /* one block each way */
-    Stage st(h);
-    const int32_t* dg = st.in(gidx, (size_t)n);
-    const uint8_t* ds = st.in(is_stop, (size_t)n);
-    const int64_t* dh = st.in(handle, (size_t)n);
-    const int32_t *v_slot, *v_bnum, *v_bcoord, *v_med;
-    const uint8_t* v_st;
-    int32_t* o_slot = st.out<int32_t>((size_t)n, &v_slot);
-    int32_t* o_bnum = st.out<int32_t>((size_t)n, &v_bnum);
-    int32_t* o_bcoord = st.out<int32_t>((size_t)n, &v_bcoord);
-    int32_t* o_med = st.out<int32_t>((size_t)n, &v_med);
-    uint8_t* o_st = st.out<uint8_t>((size_t)n, &v_st);
-    if ((rc = st.upload()) != GPX_OK) return rc;
-    rc = propose_dev_impl(h, n, dg, ds, dh, o_slot, o_bnum, o_bcoord, o_med, o_st);
-    if (rc != GPX_OK) return rc;
-    if ((rc = st.finish()) != GPX_OK) return rc;
-    memcpy(slot, v_slot, b4);
-    memcpy(bnum, v_bnum, b4);
-    memcpy(bcoord, v_bcoord, b4);
-    memcpy(median_cp, v_med, b4);
-    memcpy(status, v_st, (size_t)n);
-    return GPX_OK;
-  }
-  H2D(h->st_i32[0], gidx, b4);
-  if (is_stop) H2D(h->st_u8[0], is_stop, (size_t)n);
-  /* staging column of the 64-bit handles: allocated on first use */
-  int64_t* d_handle = nullptr;
-  if (handle) {
-    if (!h->st_handle) {
-      rc = dev_alloc(h, &h->st_handle, (size_t)h->cfg.max_batch, false);
-      if (rc != GPX_OK) return rc;
-    }
-    d_handle = h->st_handle;
-    H2D(d_handle, handle, b4 * 2);
-  }
-  rc = propose_dev_impl(h, n, h->st_i32[0], is_stop ? h->st_u8[0] : nullptr, d_handle, h->st_i32[1],
-                        h->st_i32[2], h->st_i32[3], h->st_i32[4], h->st_u8[1]);
-  if (rc != GPX_OK) return rc;
-  D2H(slot, h->st_i32[1], b4);
-  D2H(bnum, h->st_i32[2], b4);
-  D2H(bcoord, h->st_i32[3], b4);
-  D2H(median_cp, h->st_i32[4], b4);
-  D2H(status, h->st_u8[1], (size_t)n);
-  SYNC_CHECKED(h, h->sB);
-  return GPX_OK;
-}
-
-int gpx_accept_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                     const int32_t* bcoord, const int32_t* slot, const int32_t* median_cp,
-                     const uint8_t* a_flags, int32_t* r_bnum, int32_t* r_bcoord,
-                     int32_t* r_maxcp, uint8_t* r_flags, uint8_t* status, int32_t* x_gidx,
-                     int32_t* x_first, int32_t* x_count, int32_t* n_runs) {
-  int rc = check_batch(h, n);
-  if (rc != GPX_OK) return rc;
-  if (!n_runs) return GPX_EINVAL;
-  *n_runs = 0;
-  if (n == 0) return GPX_OK;
-  const size_t b4 = (size_t)n * 4;
-  if (n <= GPX_STAGE_N) { /* one block each way */
-    Stage st(h);
-    const int32_t* dg = st.in(gidx, (size_t)n);
-    const int32_t* db = st.in(bnum, (size_t)n);
-    const int32_t* dc = st.in(bcoord, (size_t)n);
-    const int32_t* dsl = st.in(slot, (size_t)n);
-    const int32_t* dm = st.in(median_cp, (size_t)n);
-    const uint8_t* df = st.in(a_flags, (size_t)n);
-    const int32_t *v_rb, *v_rc, *v_rm, *v_xg, *v_xf, *v_xc, *v_nr;
-    const uint8_t *v_rf, *v_st;
-    int32_t* o_rb = st.out<int32_t>((size_t)n, &v_rb);
-    int32_t* o_rc = st.out<int32_t>((size_t)n, &v_rc);
-    int32_t* o_rm = st.out<int32_t>((size_t)n, &v_rm);
-    uint8_t* o_rf = st.out<uint8_t>((size_t)n, &v_rf);
-    uint8_t* o_st = st.out<uint8_t>((size_t)n, &v_st);
-    int32_t* o_xg = st.out<int32_t>((size_t)n, &v_xg);
-    int32_t* o_xf = st.out<int32_t>((size_t)n, &v_xf);
-    int32_t* o_xc = st.out<int32_t>((size_t)n, &v_xc);
-    int32_t* o_nr = st.out<int32_t>(4, &v_nr);
-    if ((rc = st.upload()) != GPX_OK) return rc;
-    h->lazy_override = 0; /* one block comes back, whatever the batch: its columns must be dense (no GPX_LAZY_OUTPUTS here) */
-    rc = gpx_accept_batch_dev(h, n, dg, db, dc, dsl, dm, df, o_rb, o_rc, o_rm, o_rf, o_st, o_xg, o_xf, o_xc, o_nr);
-    h->lazy_override = -1;
-    h->last.kind = 0;
-    if (rc != GPX_OK) return rc;
-    if ((rc = st.finish()) != GPX_OK) return rc;
-    memcpy(r_bnum, v_rb, b4);
-    memcpy(r_bcoord, v_rc, b4);
-    memcpy(r_maxcp, v_rm, b4);
-    memcpy(r_flags, v_rf, (size_t)n);
-    memcpy(status, v_st, (size_t)n);
-    *n_runs = v_nr[0];
-    const size_t m4 = (size_t)(*n_runs) * 4;
-    memcpy(x_gidx, v_xg, m4);
-    memcpy(x_first, v_xf, m4);
-    memcpy(x_count, v_xc, m4);
-    return GPX_OK;
-  }
-  H2D(h->st_i32[0], gidx, b4);
-  H2D(h->st_i32[1], bnum, b4);
-  H2D(h->st_i32[2], bcoord, b4);
-  H2D(h->st_i32[3], slot, b4);
-  H2D(h->st_i32[4], median_cp, b4);
-  if (a_flags) H2D(h->st_u8[0], a_flags, (size_t)n);
-  h->lazy_override = 1; /* the count comes to the host anyway: compaction only for a batch that needs it */
-  rc = gpx_accept_batch_dev(h, n, h->st_i32[0], h->st_i32[1], h->st_i32[2], h->st_i32[3],
-                            h->st_i32[4], a_flags ? h->st_u8[0] : nullptr, h->st_i32[5],
-                            h->st_i32[6], h->st_i32[7], h->st_u8[1], h->st_u8[2], h->st_i32[8],
-                            h->st_i32[9], h->st_i32[10], h->st_count);
-  h->lazy_override = -1;
-  if (rc != GPX_OK) return rc;
-  D2H(n_runs, h->st_count, 4);
-  if (h->last.kind) {
-    SYNC_CHECKED(h, h->sB);
-    if (*n_runs < 0) {
-      if ((rc = gpx_compact_last_dev(h)) != GPX_OK) return rc;
-      D2H(n_runs, h->st_count, 4);
-    }
-    h->last.kind = 0;
-  }
-  D2H(r_bnum, h->st_i32[5], b4);
-  D2H(r_bcoord, h->st_i32[6], b4);
-  D2H(r_maxcp, h->st_i32[7], b4);
-  D2H(r_flags, h->st_u8[1], (size_t)n);
-  D2H(status, h->st_u8[2], (size_t)n);
-  SYNC_CHECKED(h, h->sB);
-  const size_t m4 = (size_t)(*n_runs) * 4;
-  if (m4) {
-    D2H(x_gidx, h->st_i32[8], m4);
-    D2H(x_first, h->st_i32[9], m4);
-    D2H(x_count, h->st_i32[10], m4);
-    SYNC_CHECKED(h, h->sB);
-  }
-  return GPX_OK;
-}
-
-int gpx_accept_reply_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                           const int32_t* bcoord, const int32_t* slot, const int32_t* acceptor,
-                           const int32_t* max_cp, int32_t* d_gidx, int32_t* d_slot,
-                           int32_t* d_bnum, int32_t* d_bcoord, int32_t* d_median_cp,
-                           uint8_t* d_kind, int32_t* n_out, uint8_t* status) {
-  int rc = check_batch(h, n);
-  if (rc != GPX_OK) return rc;
-  if (!n_out) return GPX_EINVAL;
-  *n_out = 0;
-  if (n == 0) return GPX_OK;
-  const size_t b4 = (size_t)n * 4;
-  if (n <= GPX_STAGE_N) { /* one block each way */
-    Stage st(h);
-    const int32_t* dg = st.in(gidx, (size_t)n);
-    const int32_t* db = st.in(bnum, (size_t)n);
-    const int32_t* dc = st.in(bcoord, (size_t)n);
-    const int32_t* dsl = st.in(slot, (size_t)n);
-    const int32_t* da = st.in(acceptor, (size_t)n);
-    const int32_t* dm = st.in(max_cp, (size_t)n);
-    const int32_t *v_g, *v_s, *v_b, *v_c, *v_m, *v_no;
-    const uint8_t *v_k, *v_st;
-    int32_t* o_g = st.out<int32_t>((size_t)n, &v_g);
-    int32_t* o_s = st.out<int32_t>((size_t)n, &v_s);
-    int32_t* o_b = st.out<int32_t>((size_t)n, &v_b);
-    int32_t* o_c = st.out<int32_t>((size_t)n, &v_c);
-    int32_t* o_m = st.out<int32_t>((size_t)n, &v_m);
-    uint8_t* o_k = st.out<uint8_t>((size_t)n, &v_k);
-    uint8_t* o_st = st.out<uint8_t>((size_t)n, &v_st);
-    int32_t* o_no = st.out<int32_t>(4, &v_no);
-    if ((rc = st.upload()) != GPX_OK) return rc;
-    h->lazy_override = 0; /* one block comes back, whatever the batch: its columns must be dense (no GPX_LAZY_OUTPUTS here) */
-    rc = gpx_accept_reply_batch_dev(h, n, dg, db, dc, dsl, da, dm, o_g, o_s, o_b, o_c, o_m, o_k, o_no, o_st);
-    h->lazy_override = -1;
-    h->last.kind = 0;
-    if (rc != GPX_OK) return rc;
-    if ((rc = st.finish()) != GPX_OK) return rc;
-    *n_out = v_no[0];
-    const size_t m = (size_t)(*n_out);
-    memcpy(d_gidx, v_g, m * 4);
-    memcpy(d_slot, v_s, m * 4);
-    memcpy(d_bnum, v_b, m * 4);
-    memcpy(d_bcoord, v_c, m * 4);
-    memcpy(d_median_cp, v_m, m * 4);
-    memcpy(d_kind, v_k, m);
-    if (status) memcpy(status, v_st, (size_t)n);
-    return GPX_OK;
-  }
-  H2D(h->st_i32[0], gidx, b4);
-  H2D(h->st_i32[1], bnum, b4);
-  H2D(h->st_i32[2], bcoord, b4);
-  H2D(h->st_i32[3], slot, b4);
-  H2D(h->st_i32[4], acceptor, b4);
-  H2D(h->st_i32[5], max_cp, b4);
-  h->lazy_override = 1; /* the count comes to the host anyway: compaction only for a batch that needs it */
-  rc = gpx_accept_reply_batch_dev(h, n, h->st_i32[0], h->st_i32[1], h->st_i32[2], h->st_i32[3],
-                                  h->st_i32[4], h->st_i32[5], h->st_i32[6], h->st_i32[7],
-                                  h->st_i32[8], h->st_i32[9], h->st_i32[10], h->st_u8[0],
-                                  h->st_count, h->st_u8[1]);
-  h->lazy_override = -1;
-  if (rc != GPX_OK) return rc;
-  D2H(n_out, h->st_count, 4);
-  if (status) D2H(status, h->st_u8[1], (size_t)n);
-  SYNC_CHECKED(h, h->sB);
-  if (h->last.kind) {
-    if (*n_out < 0) {
-      if ((rc = gpx_compact_last_dev(h)) != GPX_OK) return rc;
-      D2H(n_out, h->st_count, 4);
-      SYNC_CHECKED(h, h->sB);
-    }
-    h->last.kind = 0;
-  }
-  const size_t m = (size_t)(*n_out);
-  if (m) {
-    D2H(d_gidx, h->st_i32[6], m * 4);
-    D2H(d_slot, h->st_i32[7], m * 4);
-    D2H(d_bnum, h->st_i32[8], m * 4);
-    D2H(d_bcoord, h->st_i32[9], m * 4);
-    D2H(d_median_cp, h->st_i32[10], m * 4);
-    D2H(d_kind, h->st_u8[0], m);
-    SYNC_CHECKED(h, h->sB);
-  }
-  return GPX_OK;
-}
-
-int gpx_commit_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                     const int32_t* bcoord, const int32_t* slot, const int32_t* median_cp,
-                     const uint8_t* c_kind, uint8_t* status, int32_t* x_gidx, int32_t* x_first,
-                     int32_t* x_count, int32_t* n_runs) {
-  int rc = check_batch(h, n);
-  if (rc != GPX_OK) return rc;
-  if (!n_runs) return GPX_EINVAL;
-  *n_runs = 0;
-  if (n == 0) return GPX_OK;
-  const size_t b4 = (size_t)n * 4;
-  if (n <= GPX_STAGE_N) { /* one block each way */
-    Stage st(h);
-    const int32_t* dg = st.in(gidx, (size_t)n);
-    const int32_t* db = st.in(bnum, (size_t)n);
-    const int32_t* dc = st.in(bcoord, (size_t)n);
-    const int32_t* dsl = st.in(slot, (size_t)n);
-    const int32_t* dm = st.in(median_cp, (size_t)n);
-    const uint8_t* dk = st.in(c_kind, (size_t)n);
-    const int32_t *v_xg, *v_xf, *v_xc, *v_nr;
-    const uint8_t* v_st;
-    uint8_t* o_st = st.out<uint8_t>((size_t)n, &v_st);
-    int32_t* o_xg = st.out<int32_t>((size_t)n, &v_xg);
-    int32_t* o_xf = st.out<int32_t>((size_t)n, &v_xf);
-    int32_t* o_xc = st.out<int32_t>((size_t)n, &v_xc);
-    int32_t* o_nr = st.out<int32_t>(4, &v_nr);
-    if ((rc = st.upload()) != GPX_OK) return rc;
-    h->lazy_override = 0; /* one block comes back, whatever the batch: its columns must be dense (no GPX_LAZY_OUTPUTS here) */
-    rc = gpx_commit_batch_dev(h, n, dg, db, dc, dsl, dm, dk, o_st, o_xg, o_xf, o_xc, o_nr);
-    h->lazy_override = -1;
-    h->last.kind = 0;
-    if (rc != GPX_OK) return rc;
-    if ((rc = st.finish()) != GPX_OK) return rc;
-    memcpy(status, v_st, (size_t)n);
-    *n_runs = v_nr[0];
-    const size_t m4 = (size_t)(*n_runs) * 4;
-    memcpy(x_gidx, v_xg, m4);
-    memcpy(x_first, v_xf, m4);
-    memcpy(x_count, v_xc, m4);
-    return GPX_OK;
-  }
-  H2D(h->st_i32[0], gidx, b4);
-  H2D(h->st_i32[1], bnum, b4);
-  H2D(h->st_i32[2], bcoord, b4);
-  H2D(h->st_i32[3], slot, b4);
-  H2D(h->st_i32[4], median_cp, b4);
-  if (c_kind) H2D(h->st_u8[0], c_kind, (size_t)n);
-  h->lazy_override = 1;
-  rc = gpx_commit_batch_dev(h, n, h->st_i32[0], h->st_i32[1], h->st_i32[2], h->st_i32[3],
-                            h->st_i32[4], c_kind ? h->st_u8[0] : nullptr, h->st_u8[1],
-                            h->st_i32[5], h->st_i32[6], h->st_i32[7], h->st_count);
-  h->lazy_override = -1;
-  if (rc != GPX_OK) return rc;
-  D2H(n_runs, h->st_count, 4);
-  if (h->last.kind) {
-    SYNC_CHECKED(h, h->sB);
-    if (*n_runs < 0) {
-      if ((rc = gpx_compact_last_dev(h)) != GPX_OK) return rc;
-      D2H(n_runs, h->st_count, 4);
-    }
-    h->last.kind = 0;
-  }
-  D2H(status, h->st_u8[1], (size_t)n);
-  SYNC_CHECKED(h, h->sB);
-  const size_t m4 = (size_t)(*n_runs) * 4;
-  if (m4) {
-    D2H(x_gidx, h->st_i32[5], m4);
-    D2H(x_first, h->st_i32[6], m4);
-    D2H(x_count, h->st_i32[7], m4);
-    SYNC_CHECKED(h, h->sB);
-  }
-  return GPX_OK;
-}
-
-} /* extern "C" */
-
-/* ---- asynchronous host-pointer data path ---------------------------------------------- */
-/* (include/gpx.h: inputs on a copy-in stream, kernels on the engine's stream behind them, dense outputs and
- * the count on the set's copy-out stream; gpx_engine_wait fetches exactly `count` compacted entries) */
 
 /* Compacted outputs of an asynchronous call straight into the caller's (registered, device-mapped) host
  * buffers: the count is known on the DEVICE when this runs, so exactly `count` entries cross the link without
@@ -2429,216 +2118,7 @@ __global__ __launch_bounds__(256) void k_copy_out(const int32_t* __restrict__ co
   }
 }
 
-/* ... and the other way (experiment, GPX_ASYNC_COPYIN=kernel): the input columns read straight out of the
- * caller's registered host buffers by a kernel on the copy-in stream.  Measured on the MI355X box
- * (scripts/bench_async_path.py, profiles/r03_async_variants.txt): slower than the runtime's DMA copies - 2.0 ms
- * per step against 1.45 ms - so the default stays hipMemcpyAsync per column. */
-struct CopyIn {
-  int32_t n;
-  int ncols;
-  const int32_t* src[6];
-  int32_t* dst[6];
-  const uint8_t* bsrc; /* one byte column (flags), or null */
-  uint8_t* bdst;
-};
-__global__ __launch_bounds__(256) void k_copy_in(CopyIn C) {
-  const int64_t nv = C.n >> 2; /* whole 16-byte vectors; the device columns are 16-byte aligned */
-  for (int k = 0; k < 6; k++) {
-    if (k >= C.ncols) break;
-    const int32_t* __restrict__ s = C.src[k];
-    int32_t* __restrict__ d = C.dst[k];
-    if (!((uintptr_t)s & 15)) {
-      for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += (int64_t)gridDim.x * 256)
-        ((I4*)d)[v] = ((const I4*)s)[v];
-      for (int64_t i = (nv << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < C.n; i += (int64_t)gridDim.x * 256) d[i] = s[i];
-    } else {
-      for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < C.n; i += (int64_t)gridDim.x * 256) d[i] = s[i];
-    }
-  }
-  if (C.bsrc)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < C.n; i += (int64_t)gridDim.x * 256) C.bdst[i] = C.bsrc[i];
-}
-
 namespace {
-
-/* the device address of a host buffer of `bytes` bytes INSIDE a block this engine knows to be pinned - given to
- * gpx_host_register or got from gpx_host_alloc - or null (the caller then takes the copy path, which works for any host
- * memory).  The buffer must fit in its block: a kernel running over the end of a mapping faults on the GPU.
- * Memory the engine was never told about is NOT written through a mapping, whatever the runtime says about it (until
- * round 6 hipPointerGetAttributes' "host memory" was taken on its word; scripts/probe_runtime_pins.py shows that the
- * runtime does not report its own transient pinnings that way, so this was not the fault of profiles/
- * r06_abort_backtrace.txt - but one rule is easier to keep than two).  Pinned memory from elsewhere is registered like
- * any other (gpx_host_register notes that it is pinned already). */
-void* mapped_host(gpx_engine* e, void* p, size_t bytes) {
-  if (!p) return nullptr;
-  bool known = false;
-  for (auto& r : e->registered)
-    if ((char*)p >= r.first && (char*)p < r.first + r.second) {
-      if ((char*)p + bytes > r.first + r.second) return nullptr;
-      known = true;
-      break;
-    }
-  if (!known) return nullptr;
-  void* d = nullptr;
-  if (hipHostGetDevicePointer(&d, p, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  return d;
-}
-
-/* an asynchronous call failed after some of its copies or kernels were queued: no ticket will be issued, so the
- * caller has nothing to wait on - wait here, so that it may reuse its buffers and the set's columns are quiet */
-int async_fail(gpx_engine* e, gpx_engine::AsyncSet& a, int rc) {
-  if (e->s_in) HIPQ(hipStreamSynchronize(e->s_in));
-  HIPQ(hipStreamSynchronize(e->sB));
-  if (a.s_out) HIPQ(hipStreamSynchronize(a.s_out));
-  (void)hipGetLastError();
-  return rc;
-}
-
-int async_begin(gpx_engine* e, int32_t n, gpx_engine::AsyncSet** out) {
-  int rc = check_batch(e, n);
-  if (rc != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = e->as[e->async_seq % (uint64_t)e->async_depth];
-  if (a.busy) return GPX_EBUSY;
-  if (!e->s_in) {
-    /* GPX_ASYNC_IN=engine (experiment): inputs on the engine's own stream instead of a copy stream */
-    const char* v = getenv("GPX_ASYNC_IN");
-    e->async_in_engine = v && !strcmp(v, "engine");
-    const char* f = getenv("GPX_ASYNC_FILL");
-    e->async_fill_memset = f && !strcmp(f, "memset");
-    const char* dd = getenv("GPX_ASYNC_DIRECT");
-    e->async_no_direct = dd && !strcmp(dd, "0");
-    const char* ci = getenv("GPX_ASYNC_COPYIN");
-    e->async_kernel_in = ci && !strcmp(ci, "kernel");
-    HIPCHK(hipStreamCreateWithFlags(&e->s_in, hipStreamNonBlocking));
-  }
-  if (!a.ready) {
-    const size_t N = (size_t)e->cfg.max_batch;
-    for (auto& p : a.i32)
-      if ((rc = dev_alloc(e, &p, N, false)) != GPX_OK) return rc;
-    for (auto& p : a.u8)
-      if ((rc = dev_alloc(e, &p, N, false)) != GPX_OK) return rc;
-    if ((rc = dev_alloc(e, &a.cnt, 4, true)) != GPX_OK) return rc;
-    HIPCHK(hipHostMalloc((void**)&a.h_cnt, 64, hipHostMallocDefault));
-    HIPCHK(hipStreamCreateWithFlags(&a.s_out, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&a.ev_in, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&a.ev_k, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&a.ev_cnt, hipEventDisableTiming));
-    a.ready = true;
-  }
-  a.ncols = 0;
-  a.n = n;
-  a.host_kind = nullptr;
-  a.dev_kind = nullptr;
-  a.host_count = nullptr;
-  a.po_host = nullptr;
-  a.h_cnt[0] = 0;
-  *out = &a;
-  return GPX_OK;
-}
-/* queues the input columns of a call: a DMA copy per column (from pageable memory the runtime stages it) */
-int async_inputs(gpx_engine* e, int32_t n, int ncols, const int32_t* const* hsrc, int32_t* const* ddst,
-                 const uint8_t* hb, uint8_t* db) {
-  hipStream_t st = e->async_in_engine ? e->sB : e->s_in;
-  CopyIn C{};
-  C.n = n;
-  C.ncols = ncols;
-  bool ok = e->async_kernel_in;
-  for (int k = 0; k < ncols && ok; k++) {
-    C.src[k] = (const int32_t*)mapped_host(e, (void*)hsrc[k], (size_t)n * 4);
-    C.dst[k] = ddst[k];
-    ok = C.src[k] != nullptr;
-  }
-  if (ok && hb) {
-    C.bsrc = (const uint8_t*)mapped_host(e, (void*)hb, (size_t)n);
-    C.bdst = db;
-    ok = C.bsrc != nullptr;
-  }
-  if (ok) {
-    hipLaunchKernelGGL(k_copy_in, dim3(1024), dim3(256), 0, st, C);
-    return GPX_OK;
-  }
-  for (int k = 0; k < ncols; k++) HIPCHK(xfer(e, ddst[k], hsrc[k], (size_t)n * 4, hipMemcpyHostToDevice, st));
-  if (hb) HIPCHK(xfer(e, db, hb, (size_t)n, hipMemcpyHostToDevice, st));
-  return GPX_OK;
-}
-/* inputs are on their way: the kernels (engine stream) wait for them */
-int async_inputs_done(gpx_engine* e, gpx_engine::AsyncSet& a) {
-  if (e->async_in_engine) return GPX_OK;
-  HIPCHK(hipEventRecord(a.ev_in, e->s_in));
-  HIPCHK(hipStreamWaitEvent(e->sB, a.ev_in, 0));
-  return GPX_OK;
-}
-/* kernels are queued: the copy-out stream waits for them */
-int async_kernels_done(gpx_engine* e, gpx_engine::AsyncSet& a) {
-  HIPCHK(hipEventRecord(a.ev_k, e->sB));
-  HIPCHK(hipStreamWaitEvent(a.s_out, a.ev_k, 0));
-  return GPX_OK;
-}
-/* dense per-record outputs (n entries each): one k_copy_out into registered memory, else a copy per column */
-int async_dense_out(gpx_engine* e, gpx_engine::AsyncSet& a, int32_t n, int ncols, int32_t* const* hdst,
-                    const int32_t* const* dsrc, int nb, uint8_t* const* hb, const uint8_t* const* db) {
-  CopyOut C{};
-  C.ncols = ncols;
-  C.nb = nb;
-  C.fixed_n = n;
-  bool ok = !e->async_no_direct;
-  for (int k = 0; k < ncols && ok; k++) {
-    C.src[k] = dsrc[k];
-    C.dst[k] = (int32_t*)mapped_host(e, hdst[k], (size_t)n * 4);
-    ok = C.dst[k] != nullptr;
-  }
-  for (int k = 0; k < nb && ok; k++) {
-    C.bsrc[k] = db[k];
-    C.bdst[k] = (uint8_t*)mapped_host(e, hb[k], (size_t)n);
-    ok = C.bdst[k] != nullptr;
-  }
-  /* (a kernel writing through the host mapping moves about 31 GB/s where a lone DMA copy moves 48 with the other direction
-   * busy - but DMA copies for the big dense columns, tried in round 5, queue behind the copy-in stream's DMA: 2.35 ms per
-   * step against 1.33, profiles/r05_bench_e2e_dense_dma.json) */
-  if (ok) {
-    hipLaunchKernelGGL(k_copy_out, dim3(512), dim3(256), 0, a.s_out, (const int32_t*)nullptr, C);
-    return GPX_OK;
-  }
-  for (int k = 0; k < ncols; k++) HIPCHK(xfer(e, hdst[k], dsrc[k], (size_t)n * 4, hipMemcpyDeviceToHost, a.s_out));
-  for (int k = 0; k < nb; k++) HIPCHK(xfer(e, hb[k], db[k], (size_t)n, hipMemcpyDeviceToHost, a.s_out));
-  return GPX_OK;
-}
-
-int async_submit(gpx_engine* e, gpx_engine::AsyncSet& a, bool with_count, gpx_ticket* ticket) {
-  a.direct = false;
-  if (with_count && a.ncols > 0 && !e->async_no_direct) {
-    /* every compacted output column in registered memory: a kernel writes exactly `count` entries there */
-    CopyOut C{};
-    C.ncols = a.ncols;
-    bool ok = true;
-    for (int k = 0; k < a.ncols && ok; k++) {
-      C.src[k] = a.dev_col[k];
-      C.dst[k] = (int32_t*)mapped_host(e, a.host_col[k], (size_t)a.n * 4);
-      ok = C.dst[k] != nullptr;
-    }
-    if (ok && a.host_kind) {
-      C.nb = 1;
-      C.bsrc[0] = a.dev_kind;
-      C.bdst[0] = (uint8_t*)mapped_host(e, a.host_kind, (size_t)a.n);
-      ok = C.bdst[0] != nullptr;
-    }
-    C.count_dst = ok ? (int32_t*)mapped_host(e, a.host_count, 4) : nullptr;
-    if (ok && C.count_dst) {
-      hipLaunchKernelGGL(k_copy_out, dim3(512), dim3(256), 0, a.s_out, (const int32_t*)a.cnt, C);
-      a.direct = true;
-    }
-  }
-  if (with_count && !a.direct) HIPCHK(hipMemcpyAsync(a.h_cnt, a.cnt, sizeof(int32_t), hipMemcpyDeviceToHost, a.s_out));
-  HIPCHK(hipEventRecord(a.ev_cnt, a.s_out));
-  a.busy = true;
-  a.ticket = ++e->async_seq; /* > 0; the next call takes the next set */
-  *ticket = a.ticket;
-  return GPX_OK;
-}
-#define A_OUT(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyDeviceToHost, a.s_out))
 
 /* ---- packed outputs (include/gpx_packed_out.h) ---- */
 /* the two pack launches over up to `cap` entries of S on the engine's stream; n_dev = the device count, or null for cap */
@@ -2654,167 +2134,9 @@ int po_pack(gpx_engine* h, const int32_t* n_dev, int32_t cap, const PoSrc& S, vo
   HIPCHK(hipGetLastError());
   return GPX_OK;
 }
-/* the set's staging area for a packed buffer */
-int po_stage(gpx_engine* e, gpx_engine::AsyncSet& a) {
-  if (a.po_stage) return GPX_OK;
-  return dev_alloc(e, &a.po_stage, GPX_PACKED_OUT_BYTES(e->cfg.max_batch), false);
-}
-/* an empty call's buffer: the header alone, written at once */
-void po_empty(void* out, int32_t kind) {
-  const gpx_packed_out_hdr H{GPX_PO_RECORDS, kind, 0, 0, 0, 0, 0, 0};
-  memcpy(out, &H, sizeof(H));
-}
-/* the staged buffer of a call over n entries to the caller: through the mapping of a block the engine knows to be pinned
- * (the length is read on the device), else left to gpx_engine_wait, which needs the header first */
-int po_out(gpx_engine* e, gpx_engine::AsyncSet& a, void* out, size_t out_bytes, int32_t n) {
-  void* d = (e->async_no_direct || ((uintptr_t)out & 15)) ? nullptr : mapped_host(e, out, GPX_PACKED_OUT_BYTES(n));
-  if (d && !((uintptr_t)d & 15)) {
-    hipLaunchKernelGGL(k_po_copy_out, dim3(512), dim3(256), 0, a.s_out, (const uint4*)a.po_stage, (uint4*)d,
-                       (int64_t)GPX_PACKED_OUT_BYTES(n));
-    return GPX_OK;
-  }
-  HIPCHK(hipMemcpyAsync(a.h_cnt, a.po_stage, sizeof(gpx_packed_out_hdr), hipMemcpyDeviceToHost, a.s_out));
-  a.po_host = out;
-  a.po_bytes = out_bytes;
-  return GPX_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int gpx_propose_batch_async(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop, int32_t* slot,
-                            int32_t* bnum, int32_t* bcoord, int32_t* median_cp, uint8_t* status,
-                            gpx_ticket* ticket) {
-  if (!h || !ticket || (n > 0 && (!gidx || !slot || !bnum || !bcoord || !median_cp || !status))) return GPX_EINVAL;
-  gpx_engine::AsyncSet* ap = nullptr;
-  int rc = async_begin(h, n, &ap);
-  if (rc != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  if (n > 0) {
-    {
-      const int32_t* hs[1] = {gidx};
-      int32_t* dd[1] = {a.i32[0]};
-      if ((rc = async_inputs(h, n, 1, hs, dd, is_stop, a.u8[0])) != GPX_OK) return async_fail(h, a, rc);
-    }
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    rc = propose_dev_impl(h, n, a.i32[0], is_stop ? a.u8[0] : nullptr, nullptr, a.i32[1], a.i32[2], a.i32[3],
-                          a.i32[4], a.u8[1]);
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    {
-      int32_t* hd[4] = {slot, bnum, bcoord, median_cp};
-      const int32_t* ds[4] = {a.i32[1], a.i32[2], a.i32[3], a.i32[4]};
-      uint8_t* hb[1] = {status};
-      const uint8_t* db[1] = {a.u8[1]};
-      if ((rc = async_dense_out(h, a, n, 4, hd, ds, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
-    }
-  }
-  rc = async_submit(h, a, false, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
-
-int gpx_accept_batch_async(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                           const int32_t* bcoord, const int32_t* slot, const int32_t* median_cp,
-                           const uint8_t* a_flags, int32_t* r_bnum, int32_t* r_bcoord, int32_t* r_maxcp,
-                           uint8_t* r_flags, uint8_t* status, int32_t* x_gidx, int32_t* x_first,
-                           int32_t* x_count, int32_t* n_runs, gpx_ticket* ticket) {
-  if (!h || !ticket || !n_runs) return GPX_EINVAL;
-  if (n > 0 && (!gidx || !bnum || !bcoord || !slot || !median_cp || !r_bnum || !r_bcoord || !r_maxcp || !r_flags ||
-                !status || !x_gidx || !x_first || !x_count))
-    return GPX_EINVAL;
-  gpx_engine::AsyncSet* ap = nullptr;
-  int rc = async_begin(h, n, &ap);
-  if (rc != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  a.host_count = n_runs;
-  *n_runs = 0;
-  if (n > 0) {
-    {
-      const int32_t* hs[5] = {gidx, bnum, bcoord, slot, median_cp};
-      int32_t* dd[5] = {a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4]};
-      if ((rc = async_inputs(h, n, 5, hs, dd, a_flags, a.u8[0])) != GPX_OK) return async_fail(h, a, rc);
-    }
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    h->lazy_override = 0; /* k_copy_out reads the count on the device: dense columns, always */
-    rc = gpx_accept_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a_flags ? a.u8[0] : nullptr,
-                              a.i32[5], a.i32[6], a.i32[7], a.u8[1], a.u8[2], a.i32[8], a.i32[9], a.i32[10], a.cnt);
-    h->lazy_override = -1;
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    {
-      int32_t* hd[3] = {r_bnum, r_bcoord, r_maxcp};
-      const int32_t* ds[3] = {a.i32[5], a.i32[6], a.i32[7]};
-      uint8_t* hb[2] = {r_flags, status};
-      const uint8_t* db[2] = {a.u8[1], a.u8[2]};
-      if ((rc = async_dense_out(h, a, n, 3, hd, ds, 2, hb, db)) != GPX_OK) return async_fail(h, a, rc);
-    }
-    a.ncols = 3;
-    a.host_col[0] = x_gidx, a.host_col[1] = x_first, a.host_col[2] = x_count;
-    a.dev_col[0] = a.i32[8], a.dev_col[1] = a.i32[9], a.dev_col[2] = a.i32[10];
-  }
-  rc = async_submit(h, a, n > 0, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
-
-int gpx_accept_reply_batch_async(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                                 const int32_t* bcoord, int32_t common_bnum, int32_t common_bcoord,
-                                 const int32_t* slot, const int32_t* acceptor, const int32_t* max_cp,
-                                 int32_t* d_gidx, int32_t* d_slot, int32_t* d_bnum, int32_t* d_bcoord,
-                                 int32_t* d_median_cp, uint8_t* d_kind, int32_t* n_out, uint8_t* status,
-                                 gpx_ticket* ticket) {
-  if (!h || !ticket || !n_out || (bnum == nullptr) != (bcoord == nullptr)) return GPX_EINVAL;
-  if (n > 0 && (!gidx || !slot || !acceptor || !max_cp || !d_gidx || !d_slot || !d_bnum || !d_bcoord ||
-                !d_median_cp || !d_kind))
-    return GPX_EINVAL;
-  gpx_engine::AsyncSet* ap = nullptr;
-  int rc = async_begin(h, n, &ap);
-  if (rc != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  a.host_count = n_out;
-  *n_out = 0;
-  if (n > 0) {
-    if (bnum) {
-      const int32_t* hs[6] = {gidx, bnum, bcoord, slot, acceptor, max_cp};
-      int32_t* dd[6] = {a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5]};
-      if ((rc = async_inputs(h, n, 6, hs, dd, nullptr, nullptr)) != GPX_OK) return async_fail(h, a, rc);
-    } else { /* one ballot for the whole batch: the two columns are made on the device */
-      const int32_t* hs[4] = {gidx, slot, acceptor, max_cp};
-      int32_t* dd[4] = {a.i32[0], a.i32[3], a.i32[4], a.i32[5]};
-      if ((rc = async_inputs(h, n, 4, hs, dd, nullptr, nullptr)) != GPX_OK) return async_fail(h, a, rc);
-      hipStream_t fs = h->async_in_engine ? h->sB : h->s_in;
-      if (h->async_fill_memset) {
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)a.i32[1], common_bnum, (size_t)n, fs));
-        HIPCHK(hipMemsetD32Async((hipDeviceptr_t)a.i32[2], common_bcoord, (size_t)n, fs));
-      } else {
-        hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(n)), dim3(GPX_BLOCK), 0, fs, n, common_bnum, a.i32[1]);
-        hipLaunchKernelGGL(k_fill_i32, dim3(grid_for(n)), dim3(GPX_BLOCK), 0, fs, n, common_bcoord, a.i32[2]);
-      }
-    }
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    h->lazy_override = 0; /* k_copy_out reads the count on the device: dense columns, always */
-    rc = gpx_accept_reply_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5], a.i32[6],
-                                    a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.cnt, a.u8[1]);
-    h->lazy_override = -1;
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    if (status) {
-      uint8_t* hb[1] = {status};
-      const uint8_t* db[1] = {a.u8[1]};
-      if ((rc = async_dense_out(h, a, n, 0, nullptr, nullptr, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
-    }
-    a.ncols = 5;
-    int32_t* hc[5] = {d_gidx, d_slot, d_bnum, d_bcoord, d_median_cp};
-    for (int k = 0; k < 5; k++) {
-      a.host_col[k] = hc[k];
-      a.dev_col[k] = a.i32[6 + k];
-    }
-    a.host_kind = d_kind;
-    a.dev_kind = a.u8[0];
-  }
-  rc = async_submit(h, a, n > 0, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
 
 /* ---- packed votes (include/gpx_packed.h) ---- */
 static int packed_check(gpx_engine* h, const gpx_packed_votes* pv) {
@@ -2854,62 +2176,6 @@ int gpx_accept_reply_packed_dev(gpx_engine* h, const gpx_packed_votes* pv, int32
                                     d_bnum, d_bcoord, d_median_cp, d_kind, n_out, status);
 }
 
-/* queues a packed call's inputs: 8 bytes per vote and 32 per exception row cross the link, then k_votes_unpack makes
- * the set's six columns of them on the same stream (where the common-ballot form runs k_fill_i32) */
-static int packed_inputs(gpx_engine* h, gpx_engine::AsyncSet& a, const gpx_packed_votes* pv) {
-  hipStream_t fs = h->async_in_engine ? h->sB : h->s_in;
-  HIPCHK(xfer(h, a.pk_rec, pv->rec, (size_t)pv->n * 8, hipMemcpyHostToDevice, fs));
-  if (pv->n_exc > 0) HIPCHK(xfer(h, a.pk_exc, pv->exc, (size_t)pv->n_exc * 32, hipMemcpyHostToDevice, fs));
-  hipLaunchKernelGGL(k_votes_unpack, dim3(grid_for(votes_unpack_lanes(pv->n))), dim3(GPX_BLOCK), 0, fs, packed_hdr(*pv),
-                     (const uint4*)a.pk_rec, (const int32_t*)a.pk_exc, (int4*)a.i32[0], (int4*)a.i32[1], (int4*)a.i32[2],
-                     (int4*)a.i32[3], (int4*)a.i32[4], (int4*)a.i32[5]);
-  return GPX_OK;
-}
-
-int gpx_accept_reply_packed_async(gpx_engine* h, const gpx_packed_votes* pv, int32_t* d_gidx, int32_t* d_slot,
-                                  int32_t* d_bnum, int32_t* d_bcoord, int32_t* d_median_cp, uint8_t* d_kind,
-                                  int32_t* n_out, uint8_t* status, gpx_ticket* ticket) {
-  if (!ticket || !n_out) return GPX_EINVAL;
-  int rc = packed_check(h, pv);
-  if (rc != GPX_OK) return rc;
-  const int32_t n = pv->n;
-  if (n > 0 && (!d_gidx || !d_slot || !d_bnum || !d_bcoord || !d_median_cp || !d_kind)) return GPX_EINVAL;
-  gpx_engine::AsyncSet* ap = nullptr;
-  rc = async_begin(h, n, &ap);
-  if (rc != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  const size_t N = (size_t)h->cfg.max_batch;
-  if (!a.pk_rec && (rc = dev_alloc(h, &a.pk_rec, 2 * N, false)) != GPX_OK) return rc;
-  if (!a.pk_exc && (rc = dev_alloc(h, &a.pk_exc, 8 * (N / GPX_PACKED_EXC_DIV), false)) != GPX_OK) return rc;
-  a.host_count = n_out;
-  *n_out = 0;
-  if (n > 0) {
-    if ((rc = packed_inputs(h, a, pv)) != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    h->lazy_override = 0; /* k_copy_out reads the count on the device: dense columns, always */
-    rc = gpx_accept_reply_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5], a.i32[6],
-                                    a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.cnt, a.u8[1]);
-    h->lazy_override = -1;
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    if (status) {
-      uint8_t* hb[1] = {status};
-      const uint8_t* db[1] = {a.u8[1]};
-      if ((rc = async_dense_out(h, a, n, 0, nullptr, nullptr, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
-    }
-    a.ncols = 5;
-    int32_t* hc[5] = {d_gidx, d_slot, d_bnum, d_bcoord, d_median_cp};
-    for (int k = 0; k < 5; k++) {
-      a.host_col[k] = hc[k];
-      a.dev_col[k] = a.i32[6 + k];
-    }
-    a.host_kind = d_kind;
-    a.dev_kind = a.u8[0];
-  }
-  rc = async_submit(h, a, n > 0, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
-
 /* ---- packed outputs (include/gpx_packed_out.h) ---- */
 int gpx_decisions_pack_dev(gpx_engine* h, const int32_t* n_out_dev, int32_t cap, const int32_t* d_gidx,
                            const int32_t* d_slot, const int32_t* d_bnum, const int32_t* d_bcoord,
@@ -2931,151 +2197,9 @@ int gpx_proposals_pack_dev(gpx_engine* h, int32_t n, const int32_t* slot, const 
   return po_pack<GPX_PO_PROPOSALS>(h, nullptr, n, PoSrc{nullptr, slot, bnum, bcoord, median_cp, status}, out_dev);
 }
 
-int gpx_propose_packed_out_async(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop, void* out,
-                                 size_t out_bytes, gpx_ticket* ticket) {
-  if (!h || !ticket || !out || (n > 0 && !gidx)) return GPX_EINVAL;
-  int rc = check_batch(h, n);
-  if (rc != GPX_OK) return rc;
-  if (out_bytes < GPX_PACKED_OUT_BYTES(n)) return GPX_ECAPACITY;
-  gpx_engine::AsyncSet* ap = nullptr;
-  if ((rc = async_begin(h, n, &ap)) != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  if ((rc = po_stage(h, a)) != GPX_OK) return rc;
-  if (n > 0) {
-    {
-      const int32_t* hs[1] = {gidx};
-      int32_t* dd[1] = {a.i32[0]};
-      if ((rc = async_inputs(h, n, 1, hs, dd, is_stop, a.u8[0])) != GPX_OK) return async_fail(h, a, rc);
-    }
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    rc = propose_dev_impl(h, n, a.i32[0], is_stop ? a.u8[0] : nullptr, nullptr, a.i32[1], a.i32[2], a.i32[3],
-                          a.i32[4], a.u8[1]);
-    if (rc == GPX_OK) rc = gpx_proposals_pack_dev(h, n, a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.u8[1], a.po_stage);
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = po_out(h, a, out, out_bytes, n)) != GPX_OK) return async_fail(h, a, rc);
-  } else {
-    po_empty(out, GPX_PO_PROPOSALS);
-  }
-  rc = async_submit(h, a, false, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
-
-int gpx_accept_reply_packed_io_async(gpx_engine* h, const gpx_packed_votes* pv, void* out, size_t out_bytes,
-                                     uint8_t* status, gpx_ticket* ticket) {
-  if (!ticket || !out) return GPX_EINVAL;
-  int rc = packed_check(h, pv);
-  if (rc != GPX_OK) return rc;
-  const int32_t n = pv->n;
-  if (out_bytes < GPX_PACKED_OUT_BYTES(n)) return GPX_ECAPACITY;
-  gpx_engine::AsyncSet* ap = nullptr;
-  if ((rc = async_begin(h, n, &ap)) != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  const size_t N = (size_t)h->cfg.max_batch;
-  if (!a.pk_rec && (rc = dev_alloc(h, &a.pk_rec, 2 * N, false)) != GPX_OK) return rc;
-  if (!a.pk_exc && (rc = dev_alloc(h, &a.pk_exc, 8 * (N / GPX_PACKED_EXC_DIV), false)) != GPX_OK) return rc;
-  if ((rc = po_stage(h, a)) != GPX_OK) return rc;
-  if (n > 0) {
-    if ((rc = packed_inputs(h, a, pv)) != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    h->lazy_override = 0; /* the pack kernels read the count on the device: dense columns, always */
-    rc = gpx_accept_reply_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], a.i32[5], a.i32[6],
-                                    a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.cnt, a.u8[1]);
-    h->lazy_override = -1;
-    if (rc == GPX_OK)
-      rc = gpx_decisions_pack_dev(h, a.cnt, n, a.i32[6], a.i32[7], a.i32[8], a.i32[9], a.i32[10], a.u8[0], a.po_stage);
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    if (status) {
-      uint8_t* hb[1] = {status};
-      const uint8_t* db[1] = {a.u8[1]};
-      if ((rc = async_dense_out(h, a, n, 0, nullptr, nullptr, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
-    }
-    if ((rc = po_out(h, a, out, out_bytes, n)) != GPX_OK) return async_fail(h, a, rc);
-  } else {
-    po_empty(out, GPX_PO_DECISIONS);
-  }
-  rc = async_submit(h, a, false, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
-
-int gpx_commit_batch_async(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                           const int32_t* bcoord, const int32_t* slot, const int32_t* median_cp,
-                           const uint8_t* c_kind, uint8_t* status, int32_t* x_gidx, int32_t* x_first,
-                           int32_t* x_count, int32_t* n_runs, gpx_ticket* ticket) {
-  if (!h || !ticket || !n_runs) return GPX_EINVAL;
-  if (n > 0 && (!gidx || !bnum || !bcoord || !slot || !median_cp || !status || !x_gidx || !x_first || !x_count))
-    return GPX_EINVAL;
-  gpx_engine::AsyncSet* ap = nullptr;
-  int rc = async_begin(h, n, &ap);
-  if (rc != GPX_OK) return rc;
-  gpx_engine::AsyncSet& a = *ap;
-  a.host_count = n_runs;
-  *n_runs = 0;
-  if (n > 0) {
-    {
-      const int32_t* hs[5] = {gidx, bnum, bcoord, slot, median_cp};
-      int32_t* dd[5] = {a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4]};
-      if ((rc = async_inputs(h, n, 5, hs, dd, c_kind, a.u8[0])) != GPX_OK) return async_fail(h, a, rc);
-    }
-    if ((rc = async_inputs_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    h->lazy_override = 0; /* k_copy_out reads the count on the device: dense columns, always */
-    rc = gpx_commit_batch_dev(h, n, a.i32[0], a.i32[1], a.i32[2], a.i32[3], a.i32[4], c_kind ? a.u8[0] : nullptr,
-                              a.u8[1], a.i32[5], a.i32[6], a.i32[7], a.cnt);
-    h->lazy_override = -1;
-    if (rc != GPX_OK) return async_fail(h, a, rc);
-    if ((rc = async_kernels_done(h, a)) != GPX_OK) return async_fail(h, a, rc);
-    {
-      uint8_t* hb[1] = {status};
-      const uint8_t* db[1] = {a.u8[1]};
-      if ((rc = async_dense_out(h, a, n, 0, nullptr, nullptr, 1, hb, db)) != GPX_OK) return async_fail(h, a, rc);
-    }
-    a.ncols = 3;
-    a.host_col[0] = x_gidx, a.host_col[1] = x_first, a.host_col[2] = x_count;
-    a.dev_col[0] = a.i32[5], a.dev_col[1] = a.i32[6], a.dev_col[2] = a.i32[7];
-  }
-  rc = async_submit(h, a, n > 0, ticket);
-  return rc == GPX_OK ? rc : async_fail(h, a, rc);
-}
-
-int gpx_engine_wait(gpx_engine* h, gpx_ticket ticket) {
-  if (!h) return GPX_EINVAL;
-  for (auto& a : h->as) {
-    if (!a.busy || a.ticket != ticket) continue;
-    HIPCHK(hipEventSynchronize(a.ev_cnt)); /* dense outputs and the count are on the host */
-    if (int rc_abort = check_batch(h, 0)) { /* an exchange kernel of this call (or one before it) gave up: nothing to hand over */
-      a.busy = false;
-      return rc_abort;
-    }
-    if (a.po_host) { /* a packed buffer outside mapped memory: the header is here, it says how much there is to fetch */
-      void* dst = a.po_host;
-      a.po_host = nullptr;
-      const int64_t used = po_size(a.h_cnt[0], a.h_cnt[1], a.h_cnt[2], a.h_cnt[3]);
-      if (used < 32 || (uint64_t)used > a.po_bytes) {
-        a.busy = false;
-        snprintf(g_err, sizeof(g_err), "packed output header names %lld bytes for a buffer of %zu", (long long)used, a.po_bytes);
-        return GPX_EDEVICE;
-      }
-      A_OUT(dst, a.po_stage, (size_t)used);
-      SYNC_CHECKED(h, a.s_out);
-    }
-    if (a.host_count && !a.direct) {
-      const int32_t m = a.ncols ? a.h_cnt[0] : 0;
-      *a.host_count = m;
-      if (m > 0) { /* exactly m compacted entries, not the capacity */
-        for (int k = 0; k < a.ncols; k++) A_OUT(a.host_col[k], a.dev_col[k], (size_t)m * 4);
-        if (a.host_kind) A_OUT(a.host_kind, a.dev_kind, (size_t)m);
-        SYNC_CHECKED(h, a.s_out);
-      }
-    }
-    a.busy = false;
-    return GPX_OK;
-  }
-  return GPX_EBUSY; /* unknown, or already waited for */
-}
-
 } /* extern "C" */
-#undef A_OUT
+
+#include "gpx_host_calls.inc"
 
 extern "C" {
 

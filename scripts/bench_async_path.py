@@ -3,7 +3,7 @@
 gpx_propose_batch_async(1 M) + gpx_accept_reply_batch_async(3 M shuffled votes) from registered host memory,
 DEPTH steps in flight (1 = submit and wait at once: same streams, no overlap), with or without ballot columns.
 Host time inside submit() and wait() is reported separately (a runtime that copies synchronously shows up as
-submit time).  Engine experiments by environment: GPX_ASYNC_IN=engine, GPX_ASYNC_FILL=memset."""
+submit time).  Engine switch by environment: GPX_ASYNC_DIRECT=0 (outputs fetched by gpx_engine_wait)."""
 import argparse
 import ctypes as C
 import json
@@ -104,7 +104,7 @@ def main():
     ap.add_argument("--common-first", action="store_true")
     a = ap.parse_args()
     pinned = None if a.no_pin else pin_to_gpu_numa_node(0)
-    out = {"env": {k: os.environ.get(k) for k in ("GPX_ASYNC_IN", "GPX_ASYNC_FILL", "GPX_ASYNC_DIRECT", "GPX_ASYNC_COPYIN")},
+    out = {"env": {k: os.environ.get(k) for k in ("GPX_ASYNC_DIRECT",)},
            "pinned_to_gpu_numa_node": pinned is not None}
     out["sync"] = run(1, False, a.groups, a.k, a.steps, sync=True)
     for rep in range(a.repeats):  # repeats: the first configuration to touch a fresh set of device columns pays for it

@@ -60,6 +60,11 @@ class GpxPackedOutHdr(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("form", "kind", "n", "n_exc", "bnum", "bcoord", "base_slot", "base_cp")]
 
 
+class ScanCounts(C.Structure):
+    """struct gpx_scan_counts (include/gpx_scan.h)."""
+    _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -148,6 +153,14 @@ _DEV_SIGS = {
     "proposals_pack_dev": [C.c_int32] + [_VP] * 6,
     "propose_packed_out_async": [C.c_int32, _VP, _VP, _VP, C.c_size_t, C.POINTER(C.c_uint64)],
     "accept_reply_packed_io_async": [C.POINTER(GpxPackedVotes), _VP, C.c_size_t, _VP, C.POINTER(C.c_uint64)],
+    # scans that return only their hits (include/gpx_scan.h; HIP library only: the oracle's dense scans are the reference)
+    "election_scan_hits_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 5,
+    "poke_scan_hits_dev": [C.c_int32, _VP, C.c_int32] + [_VP] * 9,
+    "gap_scan_hits_dev": [C.c_int32, _VP] + [C.c_int32] * 5 + [_VP] * 6,
+    "election_scan_hits": [C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32] + [_VP] * 5,
+    "poke_scan_hits": [C.c_int32, _VP, C.c_int32] + [_VP] * 9,
+    "gap_scan_hits": [C.c_int32, _VP] + [C.c_int32] * 5 + [_VP] * 6,
+    "election_begin_hits_dev": [C.c_int32, _VP, _VP, _VP, _VP],
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],

@@ -41,26 +41,18 @@ struct PReplyOut {
   uint8_t* status;
 };
 
-/* makeCoordinator(c, bnum, myID, members, paxosState.getSlot(), recovery = false) */
-__global__ __launch_bounds__(GPX_BLOCK) void k_election_begin(DevState S, int32_t n,
-                                                             const int32_t* __restrict__ gidx,
-                                                             const int32_t* __restrict__ bnum,
-                                                             uint8_t* __restrict__ e_status) {
-  const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int32_t g = gidx[i];
-  if ((uint32_t)g >= (uint32_t)S.G || !(S.g_flags[g] & GF_EXISTS)) {
-    e_status[i] = 255;
-    return;
-  }
+/* makeCoordinator(c, bnum, myID, members, paxosState.getSlot(), recovery = false) for one group: returns its
+ * e_status.  k_election_begin and the counted form (gpx_scan.hip.h) both call it. */
+__device__ __forceinline__ uint8_t election_begin_group(const DevState& S, int32_t g, int32_t bnum) {
+  if ((uint32_t)g >= (uint32_t)S.G || !(S.g_flags[g] & GF_EXISTS)) return 255;
   const uint32_t gf = S.g_flags[g];
   const int32_t k = (int32_t)GF_K(gf);
   const bool has = (gf & GF_HASCOORD) != 0;
-  const int32_t cmp = has ? ballot_cmp(S.c_bnum[g], S.c_bcoord[g], bnum[i], S.my_id) : -1;
+  const int32_t cmp = has ? ballot_cmp(S.c_bnum[g], S.c_bcoord[g], bnum, S.my_id) : -1;
   if (!has || cmp < 0) {
     /* new PaxosCoordinatorState(bnum, myID, slot, members, null) (PCS:166-181): the previous
      * coordinator's proposals are dropped (prev == null) */
-    S.c_bnum[g] = bnum[i];
+    S.c_bnum[g] = bnum;
     S.c_bcoord[g] = S.my_id;
     S.c_next[g] = S.a_slot[g];
     S.c_pcount[g] = 0;
@@ -71,35 +63,35 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_election_begin(DevState S, int32_
       S.p_ring[o] = 0;
       S.co_ring[o] = I4{0, 0, 0, 0};
     }
-    if (bnum[i] == 0) { /* initial coordinator status assumed, not explicitly prepared (:74-76) */
+    if (bnum == 0) { /* initial coordinator status assumed, not explicitly prepared (:74-76) */
       S.g_flags[g] = (gf | GF_HASCOORD) & ~GF_PREPARING;
-      e_status[i] = GPX_EB_ACTIVE;
-    } else { /* prepare(members) arms waitforMyBallot (PCS:214-220) */
-      S.g_flags[g] = gf | GF_HASCOORD | GF_PREPARING;
-      e_status[i] = GPX_EB_PREPARING;
+      return GPX_EB_ACTIVE;
     }
-  } else if (cmp == 0 && (gf & GF_PREPARING)) {
-    e_status[i] = GPX_EB_RESEND; /* same ballot, not active: resend prepare (:80-83) */
-  } else {
-    e_status[i] = GPX_EB_UNCHANGED;
+    /* prepare(members) arms waitforMyBallot (PCS:214-220) */
+    S.g_flags[g] = gf | GF_HASCOORD | GF_PREPARING;
+    return GPX_EB_PREPARING;
   }
+  if (cmp == 0 && (gf & GF_PREPARING)) return GPX_EB_RESEND; /* same ballot, not active: resend prepare (:80-83) */
+  return GPX_EB_UNCHANGED;
 }
-
-/* pokeLocalCoordinator / PREPARE resend, minus the clocks (include/gpx.h gpx_poke_scan) */
-template <int KMAX>
-__global__ __launch_bounds__(GPX_BLOCK) void k_poke_scan(DevState S, int32_t n,
-                                                        const int32_t* __restrict__ gidx,
-                                                        uint8_t* __restrict__ poke,
-                                                        int32_t* __restrict__ slot,
-                                                        int32_t* __restrict__ bnum,
-                                                        int32_t* __restrict__ bcoord,
-                                                        int32_t* __restrict__ median_cp,
-                                                        uint8_t* __restrict__ p_flags,
-                                                        uint32_t* __restrict__ heard,
-                                                        uint8_t* __restrict__ status) {
+__global__ __launch_bounds__(GPX_BLOCK) void k_election_begin(DevState S, int32_t n,
+                                                             const int32_t* __restrict__ gidx,
+                                                             const int32_t* __restrict__ bnum,
+                                                             uint8_t* __restrict__ e_status) {
   const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const int32_t g = gidx ? gidx[i] : i;
+  e_status[i] = election_begin_group(S, gidx[i], bnum[i]);
+}
+
+/* pokeLocalCoordinator / PREPARE resend, minus the clocks (include/gpx.h gpx_poke_scan): one group's row in
+ * registers, for k_poke_scan and the hit-compacting form (gpx_scan.hip.h) */
+struct PokeRow {
+  uint8_t poke, flags, status;
+  int32_t slot, bnum, bcoord, median_cp;
+  uint32_t heard;
+};
+template <int KMAX>
+__device__ __forceinline__ PokeRow poke_scan_row(const DevState& S, int32_t g) {
   uint8_t pk = GPX_POKE_NONE, fl = 0, st = GPX_S_OK;
   int32_t sl = 0, bn = 0, bc = 0, med = 0;
   uint32_t hd = 0;
@@ -133,14 +125,30 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_poke_scan(DevState S, int32_t n,
       }
     }
   }
-  poke[i] = pk;
-  slot[i] = sl;
-  bnum[i] = bn;
-  bcoord[i] = bc;
-  median_cp[i] = med;
-  p_flags[i] = fl;
-  heard[i] = hd;
-  status[i] = st;
+  return PokeRow{pk, fl, st, sl, bn, bc, med, hd};
+}
+template <int KMAX>
+__global__ __launch_bounds__(GPX_BLOCK) void k_poke_scan(DevState S, int32_t n,
+                                                        const int32_t* __restrict__ gidx,
+                                                        uint8_t* __restrict__ poke,
+                                                        int32_t* __restrict__ slot,
+                                                        int32_t* __restrict__ bnum,
+                                                        int32_t* __restrict__ bcoord,
+                                                        int32_t* __restrict__ median_cp,
+                                                        uint8_t* __restrict__ p_flags,
+                                                        uint32_t* __restrict__ heard,
+                                                        uint8_t* __restrict__ status) {
+  const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const PokeRow r = poke_scan_row<KMAX>(S, gidx ? gidx[i] : i);
+  poke[i] = r.poke;
+  slot[i] = r.slot;
+  bnum[i] = r.bnum;
+  bcoord[i] = r.bcoord;
+  median_cp[i] = r.median_cp;
+  p_flags[i] = r.flags;
+  heard[i] = r.heard;
+  status[i] = r.status;
 }
 
 /* fe[] entry of the proposal list being built */

@@ -38,6 +38,8 @@
 #include "gpx_elect.hip.h"
 #include "gpx_packed.hip.h"
 #include "gpx_packed_out.hip.h"
+#include "../../include/gpx_scan.h"
+#include "gpx_scan.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -334,6 +336,10 @@ struct gpx_engine {
   AccScratch wa{};                 /* ACCEPT packing (gpx_wire_pack_accepts_dev), rec == nullptr until first use */
   int32_t* pk_cols = nullptr;      /* gpx_accept_reply_packed_dev: six unpacked columns, 16-byte aligned (first use) */
   int32_t* po_counts = nullptr;    /* the pack kernels' rows per workgroup, [max_batch / GPX_PO_QUAD + 1] (first use) */
+  /* hit-compacting scans (gpx_scan_host.inc): parked rows and per-tile words, and the device counts of the host twins;
+   * one block, allocated by the first such call (scan_counts != nullptr: the marker) */
+  ScanScratch scan{};
+  ScanCounts* scan_counts = nullptr;
 };
 
 namespace {
@@ -2440,3 +2446,4 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 
 #include "gpx_wire_host.inc"
 #include "gpx_elect_host.inc"
+#include "gpx_scan_host.inc"

@@ -121,8 +121,6 @@ __device__ __forceinline__ Out mk_out(int32_t gidx, int32_t slot, int32_t x, int
  * each sub-tile its share. */
 #define GPX_TILE_ITEMS (GPX_TILE / GPX_FBLOCK)
 #define GPX_TILE_VECS (GPX_TILE_ITEMS / 4)
-#define GPX_SCAN_ITEMS 8 /* records per thread in the output-flag kernels (one 8-byte load) */
-#define GPX_SCAN_TILE (GPX_FBLOCK * GPX_SCAN_ITEMS)
 #define GPX_SMALL_SEG 16  /* segments up to this long are ordered by per-lane min-scan */
 #define GPX_MIN_SHIFT 8   /* >= 256 groups per bucket */
 #define GPX_MAX_BUCKETS 4096
@@ -2181,24 +2179,16 @@ struct NodeLists {
   int32_t n_down, n_long;
   int32_t down[GPX_MAX_NODE_LIST], longdead[GPX_MAX_NODE_LIST];
 };
-__global__ __launch_bounds__(GPX_BLOCK) void k_election_scan(DevState S, int32_t n,
-                                                            const int32_t* __restrict__ gidx,
-                                                            NodeLists L, int32_t force,
-                                                            uint8_t* __restrict__ run,
-                                                            int32_t* __restrict__ p_bnum,
-                                                            int32_t* __restrict__ p_first,
-                                                            uint8_t* __restrict__ status) {
-  const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int32_t g = gidx ? gidx[i] : i;
-  run[i] = GPX_RUN_NO;
-  p_bnum[i] = 0;
-  p_first[i] = 0;
-  if ((uint32_t)g >= (uint32_t)S.G || !(S.g_flags[g] & GF_EXISTS)) {
-    status[i] = GPX_S_NOGROUP;
-    return;
-  }
-  status[i] = GPX_S_OK;
+/* one group's row of the scan, in registers: the dense kernel below and the hit-compacting one (gpx_scan.hip.h)
+ * both store what this returns */
+struct ElectionRow {
+  int32_t run, p_bnum, p_first, status;
+};
+__device__ __forceinline__ ElectionRow election_scan_row(const DevState& S, int32_t g, const NodeLists& L,
+                                                         int32_t force) {
+  ElectionRow r{GPX_RUN_NO, 0, 0, GPX_S_NOGROUP};
+  if ((uint32_t)g >= (uint32_t)S.G || !(S.g_flags[g] & GF_EXISTS)) return r;
+  r.status = GPX_S_OK;
   const uint32_t gf = S.g_flags[g];
   const int32_t k = (int32_t)GF_K(gf);
   const int32_t bn = S.a_bnum[g], bc = S.a_bcoord[g]; /* curBallot = paxosState.getBallot() */
@@ -2226,10 +2216,26 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_election_scan(DevState S, int32_t
   }
   if (why == GPX_RUN_NO && force) why = GPX_RUN_FORCED;
   if (why != GPX_RUN_NO) {
-    run[i] = (uint8_t)why;
-    p_bnum[i] = (int32_t)((uint32_t)bn + 1u); /* new Ballot(curBallot.ballotNumber + 1, myID) */
-    p_first[i] = S.a_slot[g];                 /* new PreparePacket(newBallot, paxosState.getSlot()) */
+    r.run = why;
+    r.p_bnum = (int32_t)((uint32_t)bn + 1u); /* new Ballot(curBallot.ballotNumber + 1, myID) */
+    r.p_first = S.a_slot[g];                 /* new PreparePacket(newBallot, paxosState.getSlot()) */
   }
+  return r;
+}
+__global__ __launch_bounds__(GPX_BLOCK) void k_election_scan(DevState S, int32_t n,
+                                                            const int32_t* __restrict__ gidx,
+                                                            NodeLists L, int32_t force,
+                                                            uint8_t* __restrict__ run,
+                                                            int32_t* __restrict__ p_bnum,
+                                                            int32_t* __restrict__ p_first,
+                                                            uint8_t* __restrict__ status) {
+  const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const ElectionRow r = election_scan_row(S, gidx ? gidx[i] : i, L, force);
+  run[i] = (uint8_t)r.run;
+  p_bnum[i] = r.p_bnum;
+  p_first[i] = r.p_first;
+  status[i] = (uint8_t)r.status;
 }
 
 /* ------------------------------------------------------------------------- */
@@ -2237,29 +2243,21 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_election_scan(DevState S, int32_t
 /* PaxosAcceptor.java:405-438; PISM.shouldSync, PISM:2341-2364)                  */
 /* One lane per listed group.  The committed window holds slots in [_slot, _slot + W), so the
  * missing set fits a 64-bit mask relative to _slot. */
-__global__ __launch_bounds__(GPX_BLOCK) void k_gap_scan(DevState S, int32_t n,
-                                                       const int32_t* __restrict__ gidx,
-                                                       int32_t threshold, int32_t sync_mode,
-                                                       int32_t size_limit,
-                                                       int32_t* __restrict__ first_slot,
-                                                       int32_t* __restrict__ max_committed,
-                                                       unsigned long long* __restrict__ missing,
-                                                       uint8_t* __restrict__ should_sync,
-                                                       uint8_t* __restrict__ status) {
-  const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  const int32_t g = gidx[i];
-  first_slot[i] = 0;
-  max_committed[i] = 0;
-  missing[i] = 0;
-  should_sync[i] = 0;
+/* one group's row in registers, shared by the dense kernel below and the hit-compacting one (gpx_scan.hip.h) */
+struct GapRow {
+  int32_t first_slot, max_committed;
+  unsigned long long missing;
+  int32_t should_sync, status;
+};
+__device__ __forceinline__ GapRow gap_scan_row(const DevState& S, int32_t g, int32_t threshold, int32_t sync_mode,
+                                               int32_t size_limit) {
+  GapRow r{0, 0, 0ull, 0, GPX_S_NOGROUP};
   if ((uint32_t)g >= (uint32_t)S.G || !(S.g_flags[g] & GF_EXISTS)) {
-    status[i] = GPX_S_NOGROUP;
-    return;
+    return r;
   }
   const uint32_t gf = S.g_flags[g];
   const int32_t slot = S.a_slot[g];
-  first_slot[i] = slot;
+  r.first_slot = slot;
   const bool stopped = (gf & GF_STOPPED) != 0;
   /* getMaxCommittedSlot (PaxosAcceptor.java:425-438): stopped or empty -> getSlot() - 1; else
    * committedRequests.lastKey() - the largest key in SIGNED order (a TreeMap<Integer, ..>) - and only when that key
@@ -2287,16 +2285,16 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_gap_scan(DevState S, int32_t n,
     }
     if (any) maxc = last;
   }
-  max_committed[i] = maxc;
+  r.max_committed = maxc;
   /* shouldSync (PISM:2341-2364), DISABLE_SYNC_DECISIONS = false */
   const int32_t gap = jsub(maxc, slot);
   const bool nontrivial = gap >= threshold / 100;       /* NONTRIVIAL_GAP_FACTOR */
   const bool small_thr = threshold <= 1;                /* INITIAL_SYNC_THRESHOLD */
   const bool sync = (gap >= threshold) || ((slot == 0 || slot == 1) && (nontrivial || small_thr)) ||
                     (nontrivial && sync_mode == GPX_SYNC_TO_PAUSE) || sync_mode == GPX_SYNC_FORCE;
-  should_sync[i] = sync ? 1 : 0;
-  status[i] = stopped ? GPX_S_STOPPED : GPX_S_OK;
-  if (stopped) return; /* getMissingCommittedSlots returns null */
+  r.should_sync = sync ? 1 : 0;
+  r.status = stopped ? GPX_S_STOPPED : GPX_S_OK;
+  if (stopped) return r; /* getMissingCommittedSlots returns null */
   /* missing: no commit, or a meta-commit without its accept (:414-420) */
   unsigned long long m = 0;
   const int32_t limit = (int32_t)((uint32_t)slot + (uint32_t)size_limit);
@@ -2311,7 +2309,27 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_gap_scan(DevState S, int32_t n,
     const bool acc = (ae.w & RF_PRESENT) && ae.x == s;
     if (!have || (!(cf & RF_HASVALUE) && !acc)) m |= 1ull << j;
   }
-  missing[i] = m;
+  r.missing = m;
+  return r;
+}
+
+__global__ __launch_bounds__(GPX_BLOCK) void k_gap_scan(DevState S, int32_t n,
+                                                       const int32_t* __restrict__ gidx,
+                                                       int32_t threshold, int32_t sync_mode,
+                                                       int32_t size_limit,
+                                                       int32_t* __restrict__ first_slot,
+                                                       int32_t* __restrict__ max_committed,
+                                                       unsigned long long* __restrict__ missing,
+                                                       uint8_t* __restrict__ should_sync,
+                                                       uint8_t* __restrict__ status) {
+  const int32_t i = blockIdx.x * GPX_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const GapRow r = gap_scan_row(S, gidx[i], threshold, sync_mode, size_limit);
+  first_slot[i] = r.first_slot;
+  max_committed[i] = r.max_committed;
+  missing[i] = r.missing;
+  should_sync[i] = (uint8_t)r.should_sync;
+  status[i] = (uint8_t)r.status;
 }
 
 /* ------------------------------------------------------------------------- */

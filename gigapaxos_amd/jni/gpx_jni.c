@@ -24,6 +24,7 @@
 #include "../../include/gpx.h"
 #include "../../include/gpx_wire.h"
 #include "../../include/gpx_packed.h"
+#include "../../include/gpx_scan.h"
 
 #ifdef GPX_HAVE_JNI
 #include <jni.h>
@@ -220,6 +221,28 @@ JFN(jint, gapScan)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint th
   (void)c;
   return gpx_gap_scan(H(h), n, B(gidx), threshold, syncMode, sizeLimit, B(firstSlot), B(maxCommitted),
                       B(missing), B(shouldSync), B(status));
+}
+/* the scans that return only their hits (include/gpx_scan.h): counts = a direct buffer of 16 bytes */
+JFN(jint, electionScanHits)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject down, jint nDown,
+                            jobject longDead, jint nLongDead, jint force, jint cap, jobject oGidx, jobject oRun,
+                            jobject oBnum, jobject oFirst, jobject counts) {
+  (void)c;
+  return gpx_election_scan_hits(H(h), n, B(gidx), B(down), nDown, B(longDead), nLongDead, force, cap, B(oGidx),
+                                B(oRun), B(oBnum), B(oFirst), (gpx_scan_counts*)B(counts));
+}
+JFN(jint, pokeScanHits)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint cap, jobject oGidx, jobject oPoke,
+                        jobject oSlot, jobject oBnum, jobject oBcoord, jobject oMedianCp, jobject oFlags,
+                        jobject oHeard, jobject counts) {
+  (void)c;
+  return gpx_poke_scan_hits(H(h), n, B(gidx), cap, B(oGidx), B(oPoke), B(oSlot), B(oBnum), B(oBcoord), B(oMedianCp),
+                            B(oFlags), B(oHeard), (gpx_scan_counts*)B(counts));
+}
+JFN(jint, gapScanHits)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint threshold, jint syncMode,
+                       jint sizeLimit, jint require, jint cap, jobject oGidx, jobject oFirst, jobject oMaxCommitted,
+                       jobject oMissing, jobject oSync, jobject counts) {
+  (void)c;
+  return gpx_gap_scan_hits(H(h), n, B(gidx), threshold, syncMode, sizeLimit, require, cap, B(oGidx), B(oFirst),
+                           B(oMaxCommitted), B(oMissing), B(oSync), (gpx_scan_counts*)B(counts));
 }
 #endif /* GPX_HAVE_JNI */
 

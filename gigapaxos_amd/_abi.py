@@ -65,6 +65,11 @@ class ScanCounts(C.Structure):
     _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class SweepCounts(C.Structure):
+    """struct gpx_sweep_counts (include/gpx_sweep.h)."""
+    _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("n_busy", C.c_int32), ("n_paused", C.c_int32)]
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -161,6 +166,9 @@ _DEV_SIGS = {
     "poke_scan_hits": [C.c_int32, _VP, C.c_int32] + [_VP] * 9,
     "gap_scan_hits": [C.c_int32, _VP] + [C.c_int32] * 5 + [_VP] * 6,
     "election_begin_hits_dev": [C.c_int32, _VP, _VP, _VP, _VP],
+    # the deactivation sweep (include/gpx_sweep.h; HIP library only: the oracle's retire / snapshot / dump are the reference)
+    "pause_sweep_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
+    "pause_sweep": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],

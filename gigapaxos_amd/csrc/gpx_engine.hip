@@ -40,6 +40,8 @@
 #include "gpx_packed_out.hip.h"
 #include "../../include/gpx_scan.h"
 #include "gpx_scan.hip.h"
+#include "../../include/gpx_sweep.h"
+#include "gpx_sweep.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -340,6 +342,10 @@ struct gpx_engine {
    * one block, allocated by the first such call (scan_counts != nullptr: the marker) */
   ScanScratch scan{};
   ScanCounts* scan_counts = nullptr;
+  /* deactivation sweep (gpx_sweep_host.inc): idle words over max_groups, parked hits, per-tile words and the host
+   * twin's counts; one zeroed block, allocated by the first sweep (sweep_counts != nullptr: the marker) */
+  SweepMem sweep{};
+  SweepCounts* sweep_counts = nullptr;
 };
 
 namespace {
@@ -2447,3 +2453,4 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_wire_host.inc"
 #include "gpx_elect_host.inc"
 #include "gpx_scan_host.inc"
+#include "gpx_sweep_host.inc"

@@ -2430,6 +2430,21 @@ __device__ __forceinline__ void fill_hri_dev(const DevState& S, int32_t g, uint3
   *out = r;
 }
 
+/* PaxosAcceptor.caughtUp (PaxosAcceptor.java:451-459) && PaxosCoordinator.caughtUp, in the two pieces every caller
+ * assembles: k_group_retire(PAUSE) below and the deactivation sweep (sweep_eval, gpx_sweep.hip.h).  `fl` is the flag
+ * word of one acc_ring entry: its own RF_* in bits 0-7, com_ring's at the same index above CF_SHIFT. */
+__device__ __forceinline__ bool pause_slot_busy(int32_t fl, bool from_disk) {
+  return ((((uint32_t)fl >> CF_SHIFT) & RF_PRESENT) != 0) || (!from_disk && (fl & RF_PRESENT));
+}
+__device__ __forceinline__ bool pause_coord_busy(uint32_t gf, int32_t pcount) {
+  return (gf & GF_HASCOORD) && pcount != 0;
+}
+/* what pausing or killing a live group does to the table */
+__device__ __forceinline__ void group_retire_apply(const DevState& S, int32_t g, const NameCopies& names) {
+  S.g_flags[g] = 0;
+  names.set(g, false, false, 0);
+}
+
 /* mode: 0 pause (tryPause, only if caught up), 1 kill, 2 snapshot (read only) */
 __global__ __launch_bounds__(GPX_BLOCK) void k_group_retire(DevState S, int32_t n,
                                                            const int32_t* __restrict__ gidx,
@@ -2447,25 +2462,79 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_group_retire(DevState S, int32_t 
   }
   const uint32_t gf = S.g_flags[g];
   if (mode == GPX_RETIRE_PAUSE) {
-    /* PaxosAcceptor.caughtUp (PaxosAcceptor.java:451-459) && PaxosCoordinator.caughtUp */
     bool caught = true;
     const bool from_disk = (S.flags & GPX_F_ACCEPTS_FROM_DISK) != 0;
     for (int32_t w = 0; w < S.W; w++) {
       const int64_t o = (int64_t)w * S.G + g;
-      const int32_t fl = S.acc_ring[o].w;
-      if (((uint32_t)fl >> CF_SHIFT) & RF_PRESENT) caught = false;
-      if (!from_disk && (fl & RF_PRESENT)) caught = false;
+      if (pause_slot_busy(S.acc_ring[o].w, from_disk)) caught = false;
     }
-    if ((gf & GF_HASCOORD) && S.c_pcount[g] != 0) caught = false;
+    if (pause_coord_busy(gf, S.c_pcount[g])) caught = false;
     if (!caught) {
       if (status) status[i] = GPX_S_BUSY;
       return;
     }
   }
   if (rows) fill_hri_dev(S, g, gf, &rows[i]);
-  if (mode != 2) {
-    S.g_flags[g] = 0;
-    names.set(g, false, false, 0);
-  }
+  if (mode != 2) group_retire_apply(S, g, names);
   if (status) status[i] = GPX_S_OK;
+}
+
+/* ---- deactivation sweep (include/gpx_sweep.h): one group's evaluation, in registers ---- */
+#define SWEEP_NOGROUP 0 /* out of range or dead */
+#define SWEEP_BUSY 1    /* live, gpx_group_retire(PAUSE) would answer GPX_S_BUSY */
+#define SWEEP_CAUGHT 2  /* live and caught up: sig is the signature of its state, never 0 */
+struct SweepRow {
+  int32_t kind;
+  uint32_t sig;
+};
+/* one word into the signature (the block step of MurmurHash3 x86_32) */
+__device__ __forceinline__ uint32_t sweep_mix(uint32_t h, uint32_t v) {
+  v *= 0xcc9e2d51u;
+  v = (v << 15) | (v >> 17);
+  v *= 0x1b873593u;
+  h ^= v;
+  h = (h << 13) | (h >> 19);
+  return h * 5u + 0xe6546b64u;
+}
+/* The caught-up test and the signature in ONE pass over the group's words: the state columns as coalesced dwords,
+ * every acc_ring entry whole as one 16-byte load (its flag word decides busy, all four words go into the
+ * signature).  The list of covered words is the one in include/gpx_sweep.h. */
+__device__ __forceinline__ SweepRow sweep_eval(const DevState& S, int32_t g) {
+  if ((uint32_t)g >= (uint32_t)S.G) return SweepRow{SWEEP_NOGROUP, 0u};
+  const uint32_t gf = S.g_flags[g];
+  if (!(gf & GF_EXISTS)) return SweepRow{SWEEP_NOGROUP, 0u};
+  const bool from_disk = (S.flags & GPX_F_ACCEPTS_FROM_DISK) != 0;
+  const int32_t pcount = S.c_pcount[g];
+  bool busy = pause_coord_busy(gf, pcount);
+  uint32_t h = sweep_mix(0x9747b28cu, gf);
+  h = sweep_mix(h, (uint32_t)S.g_version[g]);
+  h = sweep_mix(h, (uint32_t)S.a_slot[g]);
+  h = sweep_mix(h, (uint32_t)S.a_bnum[g]);
+  h = sweep_mix(h, (uint32_t)S.a_bcoord[g]);
+  h = sweep_mix(h, (uint32_t)S.a_gc[g]);
+  h = sweep_mix(h, (uint32_t)S.c_bnum[g]);
+  h = sweep_mix(h, (uint32_t)S.c_bcoord[g]);
+  h = sweep_mix(h, (uint32_t)S.c_next[g]);
+  h = sweep_mix(h, (uint32_t)pcount);
+  const int32_t k = min((int32_t)GF_K(gf), S.kmax);
+  for (int32_t j = 0; j < k; j++) h = sweep_mix(h, (uint32_t)S.node_slots[(int64_t)j * S.G + g]);
+#pragma unroll 4
+  for (int32_t w = 0; w < S.W; w++) {
+    const I4 e = S.acc_ring[(int64_t)w * S.G + g];
+    busy = busy || pause_slot_busy(e.w, from_disk);
+    h = sweep_mix(sweep_mix(sweep_mix(sweep_mix(h, (uint32_t)e.x), (uint32_t)e.y), (uint32_t)e.z), (uint32_t)e.w);
+  }
+  if (gf & GF_PREPARING) { /* only after gpx_election_begin: the election arrays exist */
+    h = sweep_mix(h, S.c_wait[g]);
+    for (int32_t w = 0; w < S.W; w++) {
+      const I4 e = S.co_ring[(int64_t)w * S.G + g];
+      h = sweep_mix(sweep_mix(sweep_mix(sweep_mix(h, (uint32_t)e.x), (uint32_t)e.y), (uint32_t)e.z), (uint32_t)e.w);
+    }
+  }
+  h ^= h >> 16; /* MurmurHash3's finaliser */
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return SweepRow{busy ? SWEEP_BUSY : SWEEP_CAUGHT, h ? h : 1u};
 }

@@ -25,6 +25,7 @@
 #include "../../include/gpx_wire.h"
 #include "../../include/gpx_packed.h"
 #include "../../include/gpx_scan.h"
+#include "../../include/gpx_sweep.h"
 
 #ifdef GPX_HAVE_JNI
 #include <jni.h>
@@ -243,6 +244,14 @@ JFN(jint, gapScanHits)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jin
   (void)c;
   return gpx_gap_scan_hits(H(h), n, B(gidx), threshold, syncMode, sizeLimit, require, cap, B(oGidx), B(oFirst),
                            B(oMaxCommitted), B(oMissing), B(oSync), (gpx_scan_counts*)B(counts));
+}
+/* the deactivation sweep (include/gpx_sweep.h): oRows = a direct buffer of cap rows of 100 bytes, counts = one of
+ * 16 bytes */
+JFN(jint, pauseSweep)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint minAge, jint flags, jint cap,
+                      jobject oGidx, jobject oAge, jobject oRows, jobject counts) {
+  (void)c;
+  return gpx_pause_sweep(H(h), n, B(gidx), minAge, flags, cap, B(oGidx), B(oAge), (gpx_hri*)B(oRows),
+                         (gpx_sweep_counts*)B(counts));
 }
 #endif /* GPX_HAVE_JNI */
 

@@ -1,50 +1,7 @@
-// Host side of the coordinator half of the view change (include/gpx.h, "view change, coordinator
-// side").  Included by gpx_engine.hip after gpx_wire_host.inc (TmpDev, H2D_B / D2H).
-
-namespace {
-
-/* carried-over pvalues, heard-from masks and pre-active handles: allocated by the first election */
-int elect_init(gpx_engine* e) {
-  if (e->S.c_wait) return GPX_OK;
-  const size_t G = (size_t)e->cfg.max_groups, W = (size_t)e->cfg.window;
-  int rc;
-  I4* co = nullptr;
-  int64_t *coh = nullptr, *ph = nullptr;
-  uint32_t* cw = nullptr;
-  if ((rc = dev_alloc(e, &co, G * W, true)) != GPX_OK) return rc;
-  if ((rc = dev_alloc(e, &coh, G * W, true)) != GPX_OK) return rc;
-  if ((rc = dev_alloc(e, &ph, G * W, true)) != GPX_OK) return rc;
-  if ((rc = dev_alloc(e, &cw, G, true)) != GPX_OK) return rc;
-  e->S.co_ring = co;
-  e->S.co_handle = coh;
-  e->S.p_handle = ph;
-  e->S.c_wait = cw; /* last: the marker */
-  return GPX_OK;
-}
-
-template <int KMAX>
-void launch_bucket_prepare_reply(gpx_engine* e, const PReplyIn& I, const PReplyOut& O) {
-  /* WMAX = 64 for every window: with arrays that small the compiler keeps the 8- and 16-entry
-   * variants in VGPRs and spills (150 spilled registers, 1.07 ms for the 1 M-group burst against 0.6 ms) */
-  LAUNCH_B(e, "k_bucket_prepare_reply", (k_bucket_prepare_reply<KMAX, 64>), e->S, e->X, I, O);
-}
-
-}  // namespace
+// Host-pointer side of the coordinator half of the view change (include/gpx.h, "view change, coordinator side"): each
+// call staged through CtlStage around its *_dev twin (gpx_elect_dev.inc).  Needs: gpx_host_stage.inc (CtlStage), check_batch.
 
 extern "C" {
-
-int gpx_election_begin_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
-                           uint8_t* e_status) {
-  if (!h || n < 0) return GPX_EINVAL;
-  if (n == 0) return GPX_OK;
-  if (!gidx || !bnum || !e_status) return GPX_EINVAL;
-  int rc = elect_init(h);
-  if (rc != GPX_OK) return rc;
-  h->stream = h->sB;
-  LAUNCH(h, "k_election_begin", k_election_begin, grid_for(n), h->S, n, gidx, bnum, e_status);
-  HIPCHK(hipGetLastError());
-  return GPX_OK;
-}
 
 int gpx_election_begin(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* bnum,
                        uint8_t* e_status) {
@@ -56,96 +13,14 @@ int gpx_election_begin(gpx_engine* h, int32_t n, const int32_t* gidx, const int3
     std::sort(sorted.begin(), sorted.end());
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return GPX_EINVAL;
   }
-  TmpDev t(h);
   const size_t nn = (size_t)n;
-  int32_t *d_g = t.get<int32_t>(nn), *d_b = t.get<int32_t>(nn);
-  uint8_t* d_s = t.get<uint8_t>(nn);
-  if (!d_g || !d_b || !d_s) return GPX_ENOMEM;
-  H2D_B(d_g, gidx, nn * 4);
-  H2D_B(d_b, bnum, nn * 4);
-  HIPCHK(hipStreamSynchronize(h->sB));
-  int rc = gpx_election_begin_dev(h, n, d_g, d_b, d_s);
-  if (rc != GPX_OK) return rc;
-  D2H(e_status, d_s, nn);
-  HIPCHK(hipStreamSynchronize(h->sB));
-  return GPX_OK;
-}
-
-int gpx_poke_scan(gpx_engine* h, int32_t n, const int32_t* gidx, uint8_t* poke, int32_t* slot,
-                  int32_t* bnum, int32_t* bcoord, int32_t* median_cp, uint8_t* p_flags,
-                  uint32_t* heard, uint8_t* status) {
-  if (!h || n < 0) return GPX_EINVAL;
-  if (n == 0) return GPX_OK;
-  if (!poke || !slot || !bnum || !bcoord || !median_cp || !p_flags || !heard || !status) return GPX_EINVAL;
-  TmpDev t(h);
-  const size_t nn = (size_t)n;
-  int32_t* d_g = gidx ? t.get<int32_t>(nn) : nullptr;
-  uint8_t *d_pk = t.get<uint8_t>(nn), *d_fl = t.get<uint8_t>(nn), *d_st = t.get<uint8_t>(nn);
-  int32_t *d_sl = t.get<int32_t>(nn), *d_bn = t.get<int32_t>(nn), *d_bc = t.get<int32_t>(nn);
-  int32_t* d_md = t.get<int32_t>(nn);
-  uint32_t* d_hd = t.get<uint32_t>(nn);
-  if ((gidx && !d_g) || !d_pk || !d_fl || !d_st || !d_sl || !d_bn || !d_bc || !d_md || !d_hd) return GPX_ENOMEM;
-  if (gidx) H2D_B(d_g, gidx, nn * 4);
-  if (h->cfg.kmax <= 4)
-    LAUNCH(h, "k_poke_scan", k_poke_scan<4>, grid_for(n), h->S, n, (const int32_t*)d_g, d_pk, d_sl, d_bn,
-           d_bc, d_md, d_fl, d_hd, d_st);
-  else if (h->cfg.kmax <= 8)
-    LAUNCH(h, "k_poke_scan", k_poke_scan<8>, grid_for(n), h->S, n, (const int32_t*)d_g, d_pk, d_sl, d_bn,
-           d_bc, d_md, d_fl, d_hd, d_st);
-  else
-    LAUNCH(h, "k_poke_scan", k_poke_scan<16>, grid_for(n), h->S, n, (const int32_t*)d_g, d_pk, d_sl, d_bn,
-           d_bc, d_md, d_fl, d_hd, d_st);
-  D2H(poke, d_pk, nn);
-  D2H(slot, d_sl, nn * 4);
-  D2H(bnum, d_bn, nn * 4);
-  D2H(bcoord, d_bc, nn * 4);
-  D2H(median_cp, d_md, nn * 4);
-  D2H(p_flags, d_fl, nn);
-  D2H(heard, d_hd, nn * 4);
-  D2H(status, d_st, nn);
-  HIPCHK(hipStreamSynchronize(h->sB));
-  return GPX_OK;
-}
-
-int gpx_prepare_reply_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* acceptor,
-                                const int32_t* r_bnum, const int32_t* r_bcoord,
-                                const int32_t* first_slot, const int32_t* pv_off, int32_t pv_total,
-                                const int32_t* pv_slot, const int32_t* pv_bnum,
-                                const int32_t* pv_bcoord, const int64_t* pv_handle,
-                                const uint8_t* pv_flags, uint8_t* v_kind, int32_t* e_count,
-                                int32_t* e_median, int32_t* e_slot, uint8_t* e_kind,
-                                int64_t* e_handle, uint8_t* e_flags, uint8_t* status) {
-  int rc = check_batch(h, n);
-  if (rc != GPX_OK) return rc;
-  if (n == 0) return GPX_OK;
-  if (!gidx || !acceptor || !r_bnum || !r_bcoord || !first_slot || !pv_off || pv_total < 0 || !v_kind ||
-      !e_count || !e_median || !e_slot || !e_kind || !e_handle || !e_flags || !status)
-    return GPX_EINVAL;
-  if (pv_total && (!pv_slot || !pv_bnum || !pv_bcoord)) return GPX_EINVAL;
-  if ((rc = elect_init(h)) != GPX_OK) return rc;
-  gpx_engine* e = h;
-  const size_t nn = (size_t)n, b4 = nn * 4;
-  const int fs = begin_front(e);
-  front_hist(e, n, gidx, status, 0);
-  /* payload a = acceptor, b = firstSlot, ballot = the reply's ballot */
-  launch_scatter_ac(e, n, gidx, r_bnum, r_bcoord, acceptor, first_slot, nullptr, nullptr, nullptr, nullptr,
-                    nullptr);
-  /* records of groups out of range never reach a bucket: their dense outputs are defined here */
-  HIPCHK(hipMemsetAsync(v_kind, 0, nn, e->stream));
-  HIPCHK(hipMemsetAsync(e_count, 0, b4, e->stream));
-  HIPCHK(hipMemsetAsync(e_median, 0, b4, e->stream));
-  begin_back(e, fs, n);
-  PReplyIn I{pv_off, pv_total, pv_slot, pv_bnum, pv_bcoord, pv_handle, pv_flags};
-  PReplyOut O{n, v_kind, e_count, e_median, e_slot, e_kind, e_handle, e_flags, status};
-  if (e->cfg.kmax <= 4)
-    launch_bucket_prepare_reply<4>(e, I, O);
-  else if (e->cfg.kmax <= 8)
-    launch_bucket_prepare_reply<8>(e, I, O);
-  else
-    launch_bucket_prepare_reply<16>(e, I, O);
-  end_call(e, fs);
-  HIPCHK(hipGetLastError());
-  return GPX_OK;
+  CtlStage t(h);
+  const int32_t *d_g = t.in(gidx, nn), *d_b = t.in(bnum, nn);
+  uint8_t* d_s = t.out(e_status, nn);
+  if (t.ready()) return t.rc;
+  /* no wait here: apply_streams makes the engine's front, back and launch streams one stream, the twin runs behind the copies */
+  if (t.ran(gpx_election_begin_dev(h, n, d_g, d_b, d_s))) return t.rc;
+  return t.fetch({d_s});
 }
 
 int gpx_prepare_reply_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* acceptor,
@@ -166,54 +41,24 @@ int gpx_prepare_reply_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const
     if (pv_off[i + 1] < pv_off[i]) return GPX_EINVAL;
   const size_t m = (size_t)pv_off[n];
   if (m && (!pv_slot || !pv_bnum || !pv_bcoord)) return GPX_EINVAL;
-  TmpDev t(h);
-  const size_t nn = (size_t)n, W = (size_t)h->S.W;
-  const int32_t* src[5] = {gidx, acceptor, r_bnum, r_bcoord, first_slot};
-  int32_t* in[5];
-  for (int q = 0; q < 5; q++) {
-    if (!(in[q] = t.get<int32_t>(nn))) return GPX_ENOMEM;
-    H2D_B(in[q], src[q], nn * 4);
-  }
-  int32_t* d_off = t.get<int32_t>(nn + 1);
-  int32_t *d_ps = t.get<int32_t>(m), *d_pb = t.get<int32_t>(m), *d_pc = t.get<int32_t>(m);
-  int64_t* d_ph = pv_handle ? t.get<int64_t>(m) : nullptr;
-  uint8_t* d_pf = pv_flags ? t.get<uint8_t>(m) : nullptr;
-  if (!d_off || !d_ps || !d_pb || !d_pc || (pv_handle && !d_ph) || (pv_flags && !d_pf)) return GPX_ENOMEM;
-  H2D_B(d_off, pv_off, (nn + 1) * 4);
-  if (m) {
-    H2D_B(d_ps, pv_slot, m * 4);
-    H2D_B(d_pb, pv_bnum, m * 4);
-    H2D_B(d_pc, pv_bcoord, m * 4);
-    if (d_ph) H2D_B(d_ph, pv_handle, m * 8);
-    if (d_pf) H2D_B(d_pf, pv_flags, m);
-  }
-  uint8_t *d_vk = t.get<uint8_t>(nn), *d_st = t.get<uint8_t>(nn);
-  int32_t *d_ec = t.get<int32_t>(nn), *d_em = t.get<int32_t>(nn), *d_es = t.get<int32_t>(nn * W);
-  uint8_t *d_ek = t.get<uint8_t>(nn * W), *d_ef = t.get<uint8_t>(nn * W);
-  int64_t* d_eh = t.get<int64_t>(nn * W);
-  if (!d_vk || !d_st || !d_ec || !d_em || !d_es || !d_ek || !d_ef || !d_eh) return GPX_ENOMEM;
-  /* the temporaries were filled on sB; the front end runs on the front stream */
-  HIPCHK(hipStreamSynchronize(h->sB));
-  rc = gpx_prepare_reply_batch_dev(h, n, in[0], in[1], in[2], in[3], in[4], d_off, (int32_t)m, d_ps, d_pb,
-                                   d_pc, d_ph, d_pf, d_vk, d_ec, d_em, d_es, d_ek, d_eh, d_ef, d_st);
-  if (rc != GPX_OK) return rc;
-  const size_t b4 = nn * 4;
-  D2H(v_kind, d_vk, nn);
-  D2H(status, d_st, nn);
-  D2H(e_count, d_ec, b4);
-  D2H(e_median, d_em, b4);
-  D2H(e_slot, d_es, b4 * W);
-  D2H(e_kind, d_ek, nn * W);
-  D2H(e_flags, d_ef, nn * W);
-  D2H(e_handle, d_eh, nn * W * 8);
-  HIPCHK(hipStreamSynchronize(h->sB));
-  return GPX_OK;
-}
-
-int gpx_propose_batch_h_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop,
-                            const int64_t* handle, int32_t* slot, int32_t* bnum, int32_t* bcoord,
-                            int32_t* median_cp, uint8_t* status) {
-  return propose_dev_impl(h, n, gidx, is_stop, handle, slot, bnum, bcoord, median_cp, status);
+  const size_t nn = (size_t)n, nw = nn * (size_t)h->S.W;
+  CtlStage t(h);
+  const int32_t *d_g = t.in(gidx, nn), *d_a = t.in(acceptor, nn), *d_rb = t.in(r_bnum, nn), *d_rc = t.in(r_bcoord, nn);
+  const int32_t *d_f = t.in(first_slot, nn), *d_off = t.in(pv_off, nn + 1);
+  /* the pvalues: m of them in all, none is a column of no entries (and may then be null) */
+  const int32_t *d_ps = t.in(pv_slot, m), *d_pb = t.in(pv_bnum, m), *d_pc = t.in(pv_bcoord, m);
+  const int64_t* d_ph = t.in_opt(pv_handle, m);
+  const uint8_t* d_pf = t.in_opt(pv_flags, m);
+  uint8_t *o_vk = t.out(v_kind, nn), *o_st = t.out(status, nn);
+  int32_t *o_ec = t.out(e_count, nn), *o_em = t.out(e_median, nn), *o_es = t.out(e_slot, nw);
+  uint8_t *o_ek = t.out(e_kind, nw), *o_ef = t.out(e_flags, nw);
+  int64_t* o_eh = t.out(e_handle, nw);
+  if (t.ready()) return t.rc;
+  /* no wait here either: the twin's front end runs on the one stream the copies above were queued on (apply_streams) */
+  if (t.ran(gpx_prepare_reply_batch_dev(h, n, d_g, d_a, d_rb, d_rc, d_f, d_off, (int32_t)m, d_ps, d_pb, d_pc, d_ph, d_pf,
+                                        o_vk, o_ec, o_em, o_es, o_ek, o_eh, o_ef, o_st)))
+    return t.rc;
+  return t.fetch({o_vk, o_st, o_ec, o_em, o_es, o_ek, o_ef, o_eh});
 }
 
 } /* extern "C" */

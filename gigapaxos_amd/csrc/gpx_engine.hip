@@ -195,7 +195,7 @@ struct gpx_engine {
   uint8_t* st_u8[4] = {};
   int32_t* st_count = nullptr;
   int64_t* st_handle = nullptr; /* gpx_propose_batch_h, allocated on first use */
-  /* arena of the host-pointer calls' temporary device buffers (TmpDev, gpx_wire_host.inc) */
+  /* arena of the host-pointer calls' temporary device buffers (CtlStage, gpx_host_stage.inc) */
   char* arena = nullptr;
   size_t arena_cap = 0, arena_used = 0, arena_demand = 0, arena_want = 0;
   bool arena_busy = false;
@@ -321,7 +321,7 @@ struct gpx_engine {
   std::vector<std::pair<char*, size_t>> registered;
   std::map<char*, bool> registered_own; /* block -> pinned by this engine (false: it was pinned already; not ours to unpin) */
   bool async_no_direct = false; /* GPX_ASYNC_DIRECT=0: compacted outputs fetched by gpx_engine_wait even from registered memory */
-  /* wire codec (gpx_wire_host.inc): paxosID table, row free list, scratch - allocated on first use */
+  /* wire codec (gpx_wire_dev.inc): paxosID table, row free list, scratch - allocated on first use */
   DevNames N{};
   int64_t nm_tomb = 0;
   std::vector<int32_t> free_rows;
@@ -338,11 +338,11 @@ struct gpx_engine {
   AccScratch wa{};                 /* ACCEPT packing (gpx_wire_pack_accepts_dev), rec == nullptr until first use */
   int32_t* pk_cols = nullptr;      /* gpx_accept_reply_packed_dev: six unpacked columns, 16-byte aligned (first use) */
   int32_t* po_counts = nullptr;    /* the pack kernels' rows per workgroup, [max_batch / GPX_PO_QUAD + 1] (first use) */
-  /* hit-compacting scans (gpx_scan_host.inc): parked rows and per-tile words, and the device counts of the host twins;
+  /* hit-compacting scans (gpx_scan_dev.inc): parked rows and per-tile words, and the device counts of the host twins;
    * one block, allocated by the first such call (scan_counts != nullptr: the marker) */
   ScanScratch scan{};
   ScanCounts* scan_counts = nullptr;
-  /* deactivation sweep (gpx_sweep_host.inc): idle words over max_groups, parked hits, per-tile words and the host
+  /* deactivation sweep (gpx_sweep_dev.inc): idle words over max_groups, parked hits, per-tile words and the host
    * twin's counts; one zeroed block, allocated by the first sweep (sweep_counts != nullptr: the marker) */
   SweepMem sweep{};
   SweepCounts* sweep_counts = nullptr;
@@ -2082,8 +2082,6 @@ int gpx_propose_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const u
 /* H2D into device columns, the _dev twin, D2H of the results: gpx_host_calls.inc, included below */
 
 #define H2D(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyHostToDevice, h->sF))
-/* lifecycle calls change group state: everything on the back-end stream, in call order */
-#define H2D_B(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyHostToDevice, h->sB))
 #define D2H(dst, src, bytes) HIPCHK(xfer(h, (dst), (src), (bytes), hipMemcpyDeviceToHost, h->sB))
 
 /* Compacted outputs of an asynchronous call straight into the caller's (registered, device-mapped) host
@@ -2214,87 +2212,6 @@ int gpx_proposals_pack_dev(gpx_engine* h, int32_t n, const int32_t* slot, const 
 #include "gpx_host_calls.inc"
 
 extern "C" {
-
-/* ---- lifecycle ------------------------------------------------------------------ */
-
-int gpx_group_create(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* members,
-                     const uint8_t* k, const gpx_hri* rows, uint8_t* status) {
-  if (!h || n < 0) return GPX_EINVAL;
-  if (n == 0) return GPX_OK;
-  if (!gidx || !members || !k || !rows) return GPX_EINVAL;
-  /* chunked through temporary device buffers: creation is not on the data path */
-  const int32_t chunk = 1 << 18;
-  int32_t *d_g = nullptr, *d_m = nullptr;
-  uint8_t *d_k = nullptr, *d_s = nullptr;
-  gpx_hri* d_r = nullptr;
-  const int32_t c0 = std::min(n, chunk);
-  HIPCHK(hipMalloc((void**)&d_g, (size_t)c0 * 4));
-  HIPCHK(hipMalloc((void**)&d_m, (size_t)c0 * 4 * h->cfg.kmax));
-  HIPCHK(hipMalloc((void**)&d_k, (size_t)c0));
-  HIPCHK(hipMalloc((void**)&d_s, (size_t)c0));
-  HIPCHK(hipMalloc((void**)&d_r, (size_t)c0 * sizeof(gpx_hri)));
-  int rc = GPX_OK;
-  for (int32_t o = 0; o < n && rc == GPX_OK; o += chunk) {
-    const int32_t c = std::min(chunk, n - o);
-    H2D_B(d_g, gidx + o, (size_t)c * 4);
-    H2D_B(d_m, members + (size_t)o * h->cfg.kmax, (size_t)c * 4 * h->cfg.kmax);
-    H2D_B(d_k, k + o, (size_t)c);
-    H2D_B(d_r, rows + o, (size_t)c * sizeof(gpx_hri));
-    LAUNCH(h, "k_group_create", k_group_create, grid_for(c), h->S, c, (const int32_t*)d_g,
-           (const int32_t*)d_m, (const uint8_t*)d_k, (const gpx_hri*)d_r, d_s, NameCopies{h->N.rows, (uint8_t*)h->N.tab});
-    if (status) D2H(status + o, d_s, (size_t)c);
-    HIPCHK(hipStreamSynchronize(h->sB));
-    rc = check_batch(h, 0); /* (an exchange kernel that gave up before this call: the table is not to be built on) */
-  }
-  (void)hipFree(d_g);
-  (void)hipFree(d_m);
-  (void)hipFree(d_k);
-  (void)hipFree(d_s);
-  (void)hipFree(d_r);
-  return rc;
-}
-
-static int retire_impl(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t mode, gpx_hri* rows,
-                       uint8_t* status) {
-  if (!h || n < 0) return GPX_EINVAL;
-  if (n == 0) return GPX_OK;
-  if (!gidx) return GPX_EINVAL;
-  const int32_t chunk = 1 << 18;
-  int32_t* d_g = nullptr;
-  uint8_t* d_s = nullptr;
-  gpx_hri* d_r = nullptr;
-  const int32_t c0 = std::min(n, chunk);
-  HIPCHK(hipMalloc((void**)&d_g, (size_t)c0 * 4));
-  HIPCHK(hipMalloc((void**)&d_s, (size_t)c0));
-  HIPCHK(hipMalloc((void**)&d_r, (size_t)c0 * sizeof(gpx_hri)));
-  int rc = GPX_OK;
-  for (int32_t o = 0; o < n && rc == GPX_OK; o += chunk) {
-    const int32_t c = std::min(chunk, n - o);
-    H2D_B(d_g, gidx + o, (size_t)c * 4);
-    LAUNCH(h, "k_group_retire", k_group_retire, grid_for(c), h->S, c, (const int32_t*)d_g, mode, d_r,
-           d_s, NameCopies{h->N.rows, (uint8_t*)h->N.tab});
-    if (rows) D2H(rows + o, d_r, (size_t)c * sizeof(gpx_hri));
-    if (status) D2H(status + o, d_s, (size_t)c);
-    HIPCHK(hipStreamSynchronize(h->sB));
-    rc = check_batch(h, 0); /* a snapshot of a table an exchange kernel left half-written is not a snapshot */
-  }
-  (void)hipFree(d_g);
-  (void)hipFree(d_s);
-  (void)hipFree(d_r);
-  return rc;
-}
-
-int gpx_group_retire(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t mode, gpx_hri* rows,
-                     uint8_t* status) {
-  if (mode != GPX_RETIRE_PAUSE && mode != GPX_RETIRE_KILL) return GPX_EINVAL;
-  return retire_impl(h, n, gidx, mode, rows, status);
-}
-
-int gpx_group_snapshot(gpx_engine* h, int32_t n, const int32_t* gidx, gpx_hri* rows,
-                       uint8_t* status) {
-  if (!rows) return GPX_EINVAL;
-  return retire_impl(h, n, gidx, 2, rows, status);
-}
 
 /* canonical dump (same word layout as the oracle's orc_group_dump; docs/HISTORY.md §state-dump) */
 int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
@@ -2450,7 +2367,16 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 
 } /* extern "C" */
 
+/* the *_dev calls of the wire, election, scan and sweep families: their scratch, argument checks and launches */
+#include "gpx_ctl_args.inc"
+#include "gpx_wire_dev.inc"
+#include "gpx_elect_dev.inc"
+#include "gpx_scan_dev.inc"
+#include "gpx_sweep_dev.inc"
+/* the control-plane host-pointer calls: CtlStage, then each family's twins over it and the public *_dev prototypes */
+#include "gpx_host_stage.inc"
 #include "gpx_wire_host.inc"
 #include "gpx_elect_host.inc"
 #include "gpx_scan_host.inc"
 #include "gpx_sweep_host.inc"
+#include "gpx_group_host.inc"

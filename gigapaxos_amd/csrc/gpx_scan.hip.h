@@ -27,7 +27,7 @@
 // hold max(max_groups, max_batch) entries rounded up to whole tiles; the host refuses a larger n.
 #pragma once
 
-#define GPX_SCAN_TILE_ 1024 /* == GPX_SCAN_TILE of include/gpx_scan.h (checked in gpx_scan_host.inc) */
+#define GPX_SCAN_TILE_ 1024 /* == GPX_SCAN_TILE of include/gpx_scan.h (checked in gpx_scan_dev.inc) */
 #define GPX_SCAN_WAVES (GPX_BLOCK / 64)
 
 struct ScanCounts { /* == gpx_scan_counts */

@@ -1,73 +1,10 @@
-// Host side of the hit-compacting scans (include/gpx_scan.h; kernels in gpx_scan.hip.h).  Included by
-// gpx_engine.hip after gpx_elect_host.inc (elect_init, TmpDev, H2D_B / D2H).
+// Host-pointer side of the table scans: the dense election, gap and poke scans of include/gpx.h and their hit-compacting
+// forms of include/gpx_scan.h, each staged through CtlStage.
+// Needs: gpx_host_stage.inc (CtlStage), scan_args / scan_lists (gpx_ctl_args.inc), scan_open (gpx_scan_dev.inc), LAUNCH, grid_for.
 
 namespace {
 
-static_assert(GPX_SCAN_TILE == GPX_SCAN_TILE_, "include/gpx_scan.h and gpx_scan.hip.h disagree on the tile");
-static_assert(GPX_SCAN_TILE % GPX_BLOCK == 0, "a tile is whole passes of a workgroup");
-static_assert(sizeof(gpx_scan_counts) == 16 && sizeof(ScanCounts) == 16, "gpx_scan_counts is 16 bytes");
-
-inline int64_t scan_max_n(const gpx_engine* e) { return std::max<int64_t>(e->cfg.max_groups, e->cfg.max_batch); }
-
-/* The parked rows, the per-tile words and the host twins' counts: ONE block, allocated by the first scan and sized
- * once for max(max_groups, max_batch) entries in whole tiles.  Not cleared: a call reads only what it wrote
- * (gpx_scan.hip.h).  A failed allocation leaves nothing behind and the engine usable. */
-int scan_init(gpx_engine* e) {
-  if (e->scan_counts) return GPX_OK;
-  const size_t tiles = ((size_t)scan_max_n(e) + GPX_SCAN_TILE - 1) / GPX_SCAN_TILE;
-  const size_t cap = std::max<size_t>(tiles, 1) * GPX_SCAN_TILE;
-  const size_t tl = (std::max<size_t>(tiles, 1) * 4 + 255) & ~(size_t)255;
-  if (cap > UINT32_MAX) return GPX_ECAPACITY;
-  char* base = nullptr;
-  int rc = dev_alloc(e, &base, 26 * cap + 3 * tl + 256, false); /* ScanScratch's layout, then the counts */
-  if (rc != GPX_OK) return rc;
-  e->scan = ScanScratch{base, (uint32_t)cap, (uint32_t)tl};
-  e->scan_counts = (ScanCounts*)(base + 26 * cap + 3 * tl); /* last: the marker */
-  return GPX_OK;
-}
-
-/* what every scan checks before it uses the handle */
-int scan_args(const gpx_engine* h, int32_t n, int32_t cap, const void* counts, std::initializer_list<const void*> cols) {
-  if (!h || n < 0 || cap < 0 || !counts) return GPX_EINVAL;
-  if (cap > 0)
-    for (const void* c : cols)
-      if (!c) return GPX_EINVAL;
-  return GPX_OK;
-}
-int scan_lists(const int32_t* down_nodes, int32_t n_down, const int32_t* long_dead_nodes, int32_t n_long_dead,
-               NodeLists* L) {
-  if (n_down < 0 || n_long_dead < 0) return GPX_EINVAL;
-  if (n_down > GPX_MAX_NODE_LIST || n_long_dead > GPX_MAX_NODE_LIST) return GPX_ECAPACITY;
-  if ((n_down && !down_nodes) || (n_long_dead && !long_dead_nodes)) return GPX_EINVAL;
-  memset(L, 0, sizeof(*L));
-  L->n_down = n_down;
-  L->n_long = n_long_dead;
-  for (int32_t q = 0; q < n_down; q++) L->down[q] = down_nodes[q];
-  for (int32_t q = 0; q < n_long_dead; q++) L->longdead[q] = long_dead_nodes[q];
-  return GPX_OK;
-}
-/* ... and what needs the engine: the size limit, an engine an exchange kernel gave up on, the scratch */
-int scan_open(gpx_engine* h, int32_t n) {
-  if ((int64_t)n > scan_max_n(h)) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  return scan_init(h);
-}
-
-/* the three launches of one scan on the back-end stream (gpx_scan.hip.h) */
-template <class E>
-int scan_run(gpx_engine* h, const char* tile_name, const char* move_name, int32_t n, const int32_t* gidx, const E& ev,
-             int32_t cap, const ScanOut& O, gpx_scan_counts* counts) {
-  h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n + GPX_SCAN_TILE - 1) / GPX_SCAN_TILE);
-  if (ntiles) LAUNCH(h, tile_name, (k_scan_tile<E>), ntiles, h->S, n, gidx, ev, h->scan);
-  LAUNCH(h, "k_scan_offsets", k_scan_offsets, 1, (int32_t)ntiles, h->scan, (ScanCounts*)counts);
-  if (ntiles && cap > 0) LAUNCH(h, move_name, (k_scan_move<E>), ntiles, h->scan, O, cap);
-  HIPCHK(hipGetLastError());
-  return GPX_OK;
-}
-
-/* A host twin: the scanned list in, the _dev form into temporaries of min(cap, n) entries, the counts out, then
+/* A hit-compacting twin: the scanned list in, the _dev form into temporaries of min(cap, n) entries, the counts out, then
  * min(n_hits, cap) entries per column.  `dev(d_gidx, m, cols, d_counts)` queues the _dev form; cols[q] has
  * size[q] bytes per entry and goes to host[q]. */
 template <class F>
@@ -75,72 +12,84 @@ int scan_host(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t cap, int nc
               const int* size, gpx_scan_counts* counts, F dev) {
   int rc = scan_open(h, n);
   if (rc != GPX_OK) return rc;
-  TmpDev t(h);
+  CtlStage t(h);
   const int32_t m = std::min(cap, n);
-  int32_t* d_g = nullptr;
-  if (gidx && n) {
-    if (!(d_g = t.get<int32_t>((size_t)n))) return GPX_ENOMEM;
-    H2D_B(d_g, gidx, (size_t)n * 4);
-  }
+  const int32_t* d_g = n ? t.in_opt(gidx, (size_t)n) : nullptr;
   void* cols[8] = {};
-  for (int q = 0; q < ncols && m > 0; q++)
-    if (!(cols[q] = t.get<uint8_t>((size_t)m * size[q]))) return GPX_ENOMEM;
-  if ((rc = dev(d_g, m, cols, (gpx_scan_counts*)h->scan_counts)) != GPX_OK) return rc;
-  D2H(counts, h->scan_counts, sizeof(*counts));
-  HIPCHK(hipStreamSynchronize(h->sB));
+  for (int q = 0; q < ncols && m > 0; q++) cols[q] = t.out_bytes(host[q], (size_t)m, (size_t)size[q]);
+  if (t.ready()) return t.rc;
+  if (t.ran(dev(d_g, m, cols, (gpx_scan_counts*)h->scan_counts))) return t.rc;
+  t.d2h(counts, h->scan_counts, sizeof(*counts));
+  if (t.sync()) return t.rc;
   const size_t k = (size_t)std::max(0, std::min(counts->n_hits, m));
-  if (k) {
-    for (int q = 0; q < ncols; q++) D2H(host[q], cols[q], k * size[q]);
-    HIPCHK(hipStreamSynchronize(h->sB));
-  }
-  return GPX_OK;
+  if (!k) return GPX_OK;
+  for (int q = 0; q < ncols; q++) t.queue(cols[q], k);
+  return t.sync();
 }
 
 }  // namespace
 
 extern "C" {
 
-int gpx_election_scan_hits_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* down_nodes,
-                               int32_t n_down, const int32_t* long_dead_nodes, int32_t n_long_dead, int32_t force,
-                               int32_t cap, int32_t* o_gidx, uint8_t* o_run, int32_t* o_bnum, int32_t* o_first,
-                               gpx_scan_counts* counts) {
-  int rc = scan_args(h, n, cap, counts, {o_gidx, o_run, o_bnum, o_first});
+int gpx_election_scan(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* down_nodes,
+                      int32_t n_down, const int32_t* long_dead_nodes, int32_t n_long_dead,
+                      int32_t force, uint8_t* run, int32_t* p_bnum, int32_t* p_first,
+                      uint8_t* status) {
+  if (!h || n < 0 || n_down < 0 || n_long_dead < 0) return GPX_EINVAL;
+  if (n_down > GPX_MAX_NODE_LIST || n_long_dead > GPX_MAX_NODE_LIST) return GPX_ECAPACITY;
+  if (n == 0) return GPX_OK;
+  if (!run || !p_bnum || !p_first || !status) return GPX_EINVAL;
+  NodeLists L;
+  int rc = scan_lists(down_nodes, n_down, long_dead_nodes, n_long_dead, &L);
   if (rc != GPX_OK) return rc;
-  ScanElection ev;
-  if ((rc = scan_lists(down_nodes, n_down, long_dead_nodes, n_long_dead, &ev.L)) != GPX_OK) return rc;
-  ev.force = force;
-  if ((rc = scan_open(h, n)) != GPX_OK) return rc;
-  ScanOut O{};
-  O.i32[0] = o_gidx, O.u8[0] = o_run, O.i32[1] = o_bnum, O.i32[2] = o_first;
-  return scan_run(h, "k_scan_election_tile", "k_scan_election_move", n, gidx, ev, cap, O, counts);
+  const size_t nn = (size_t)n;
+  CtlStage t(h);
+  const int32_t* d_g = t.in_opt(gidx, nn);
+  uint8_t *d_r = t.out(run, nn), *d_s = t.out(status, nn);
+  int32_t *d_b = t.out(p_bnum, nn), *d_f = t.out(p_first, nn);
+  if (t.ready()) return t.rc;
+  LAUNCH(h, "k_election_scan", k_election_scan, grid_for(n), h->S, n, d_g, L, force, d_r, d_b, d_f, d_s);
+  return t.fetch({d_r, d_b, d_f, d_s});
 }
 
-int gpx_poke_scan_hits_dev(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t cap, int32_t* o_gidx,
-                           uint8_t* o_poke, int32_t* o_slot, int32_t* o_bnum, int32_t* o_bcoord,
-                           int32_t* o_median_cp, uint8_t* o_flags, uint32_t* o_heard, gpx_scan_counts* counts) {
-  int rc = scan_args(h, n, cap, counts, {o_gidx, o_poke, o_slot, o_bnum, o_bcoord, o_median_cp, o_flags, o_heard});
-  if (rc != GPX_OK) return rc;
-  if ((rc = scan_open(h, n)) != GPX_OK) return rc;
-  ScanOut O{};
-  O.i32[0] = o_gidx, O.u8[0] = o_poke, O.i32[1] = o_slot, O.i32[2] = o_bnum, O.i32[3] = o_bcoord;
-  O.i32[4] = o_median_cp, O.u8[1] = o_flags, O.i32[5] = (int32_t*)o_heard;
-  const char *tn = "k_scan_poke_tile", *mn = "k_scan_poke_move";
-  if (h->cfg.kmax <= 4) return scan_run(h, tn, mn, n, gidx, ScanPoke<4>{}, cap, O, counts);
-  if (h->cfg.kmax <= 8) return scan_run(h, tn, mn, n, gidx, ScanPoke<8>{}, cap, O, counts);
-  return scan_run(h, tn, mn, n, gidx, ScanPoke<16>{}, cap, O, counts);
+int gpx_gap_scan(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t threshold,
+                 int32_t sync_mode, int32_t size_limit, int32_t* first_slot,
+                 int32_t* max_committed, uint64_t* missing, uint8_t* should_sync, uint8_t* status) {
+  if (!h || n < 0) return GPX_EINVAL;
+  if (n == 0) return GPX_OK;
+  if (!gidx || !first_slot || !max_committed || !missing || !should_sync || !status) return GPX_EINVAL;
+  const size_t nn = (size_t)n;
+  CtlStage t(h);
+  const int32_t* d_g = t.in(gidx, nn);
+  int32_t *d_f = t.out(first_slot, nn), *d_m = t.out(max_committed, nn);
+  unsigned long long* d_mi = t.out((unsigned long long*)missing, nn);
+  uint8_t *d_sy = t.out(should_sync, nn), *d_st = t.out(status, nn);
+  if (t.ready()) return t.rc;
+  LAUNCH(h, "k_gap_scan", k_gap_scan, grid_for(n), h->S, n, d_g, threshold, sync_mode, size_limit, d_f, d_m, d_mi, d_sy,
+         d_st);
+  return t.fetch({d_f, d_m, d_mi, d_sy, d_st});
 }
 
-int gpx_gap_scan_hits_dev(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t threshold, int32_t sync_mode,
-                          int32_t size_limit, int32_t require, int32_t cap, int32_t* o_gidx, int32_t* o_first,
-                          int32_t* o_max_committed, uint64_t* o_missing, uint8_t* o_sync, gpx_scan_counts* counts) {
-  int rc = scan_args(h, n, cap, counts, {o_gidx, o_first, o_max_committed, o_missing, o_sync});
-  if (rc != GPX_OK) return rc;
-  if ((rc = scan_open(h, n)) != GPX_OK) return rc;
-  ScanOut O{};
-  O.i32[0] = o_gidx, O.i32[1] = o_first, O.i32[2] = o_max_committed, O.u64 = (unsigned long long*)o_missing;
-  O.u8[0] = o_sync;
-  return scan_run(h, "k_scan_gap_tile", "k_scan_gap_move", n, gidx, ScanGap{threshold, sync_mode, size_limit, require},
-                  cap, O, counts);
+int gpx_poke_scan(gpx_engine* h, int32_t n, const int32_t* gidx, uint8_t* poke, int32_t* slot,
+                  int32_t* bnum, int32_t* bcoord, int32_t* median_cp, uint8_t* p_flags,
+                  uint32_t* heard, uint8_t* status) {
+  if (!h || n < 0) return GPX_EINVAL;
+  if (n == 0) return GPX_OK;
+  if (!poke || !slot || !bnum || !bcoord || !median_cp || !p_flags || !heard || !status) return GPX_EINVAL;
+  const size_t nn = (size_t)n;
+  CtlStage t(h);
+  const int32_t* d_g = t.in_opt(gidx, nn);
+  uint8_t *d_pk = t.out(poke, nn), *d_fl = t.out(p_flags, nn), *d_st = t.out(status, nn);
+  int32_t *d_sl = t.out(slot, nn), *d_bn = t.out(bnum, nn), *d_bc = t.out(bcoord, nn), *d_md = t.out(median_cp, nn);
+  uint32_t* d_hd = t.out(heard, nn);
+  if (t.ready()) return t.rc;
+  if (h->cfg.kmax <= 4)
+    LAUNCH(h, "k_poke_scan", k_poke_scan<4>, grid_for(n), h->S, n, d_g, d_pk, d_sl, d_bn, d_bc, d_md, d_fl, d_hd, d_st);
+  else if (h->cfg.kmax <= 8)
+    LAUNCH(h, "k_poke_scan", k_poke_scan<8>, grid_for(n), h->S, n, d_g, d_pk, d_sl, d_bn, d_bc, d_md, d_fl, d_hd, d_st);
+  else
+    LAUNCH(h, "k_poke_scan", k_poke_scan<16>, grid_for(n), h->S, n, d_g, d_pk, d_sl, d_bn, d_bc, d_md, d_fl, d_hd, d_st);
+  return t.fetch({d_pk, d_sl, d_bn, d_bc, d_md, d_fl, d_hd, d_st});
 }
 
 int gpx_election_scan_hits(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_t* down_nodes, int32_t n_down,
@@ -189,22 +138,6 @@ int gpx_gap_scan_hits(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t thr
                                                   (int32_t*)c[0], (int32_t*)c[1], (int32_t*)c[2], (uint64_t*)c[3],
                                                   (uint8_t*)c[4], d_counts);
                    });
-}
-
-int gpx_election_begin_hits_dev(gpx_engine* h, int32_t cap, const gpx_scan_counts* counts, const int32_t* gidx,
-                                const int32_t* bnum, uint8_t* e_status) {
-  if (!h || cap < 0) return GPX_EINVAL;
-  if (cap == 0) return GPX_OK;
-  if (!counts || !gidx || !bnum || !e_status) return GPX_EINVAL;
-  if ((int64_t)cap > scan_max_n(h)) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  if ((rc = elect_init(h)) != GPX_OK) return rc;
-  h->stream = h->sB;
-  LAUNCH(h, "k_scan_election_begin", k_scan_election_begin, grid_for(cap), h->S, cap, (const ScanCounts*)counts, gidx,
-         bnum, e_status);
-  HIPCHK(hipGetLastError());
-  return GPX_OK;
 }
 
 } /* extern "C" */

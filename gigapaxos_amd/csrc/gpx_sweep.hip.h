@@ -32,7 +32,7 @@
 
 #define GPX_SWEEP_TILE 1024
 #define GPX_SWEEP_WAVES (GPX_BLOCK / 64)
-#define GPX_SWEEP_PEEK_ 1 /* == GPX_SWEEP_PEEK / GPX_SWEEP_HOLD of include/gpx_sweep.h (checked in gpx_sweep_host.inc) */
+#define GPX_SWEEP_PEEK_ 1 /* == GPX_SWEEP_PEEK / GPX_SWEEP_HOLD of include/gpx_sweep.h (checked in gpx_sweep_dev.inc) */
 #define GPX_SWEEP_HOLD_ 2
 
 struct SweepCounts { /* == gpx_sweep_counts */

@@ -1,111 +1,28 @@
-// Host side of the deactivation sweep (include/gpx_sweep.h; kernels in gpx_sweep.hip.h).  Included by gpx_engine.hip
-// after gpx_scan_host.inc (scan_max_n, TmpDev, H2D_B / D2H).
-
-namespace {
-
-static_assert(GPX_SWEEP_PEEK == GPX_SWEEP_PEEK_ && GPX_SWEEP_HOLD == GPX_SWEEP_HOLD_,
-              "include/gpx_sweep.h and gpx_sweep.hip.h disagree on the flags");
-static_assert(GPX_SWEEP_TILE % GPX_BLOCK == 0, "a tile is whole passes of a workgroup");
-static_assert(sizeof(gpx_sweep_counts) == 16 && sizeof(SweepCounts) == 16, "gpx_sweep_counts is 16 bytes");
-static_assert(sizeof(gpx_hri) == 100, "the row of gpx_group_retire");
-
-/* The idle words, the parked hits, the per-tile words and the host twin's counts: ONE block, allocated by the first
- * sweep.  Zeroed: the idle words start at "never seen" (the rest is scratch, of which a call reads only what it wrote).
- * A failed allocation leaves nothing behind and the engine usable. */
-int sweep_init(gpx_engine* e) {
-  if (e->sweep_counts) return GPX_OK;
-  const size_t G = (size_t)std::max(e->cfg.max_groups, 1);
-  const size_t tiles = std::max<size_t>(((size_t)scan_max_n(e) + GPX_SWEEP_TILE - 1) / GPX_SWEEP_TILE, 1);
-  const size_t cap = tiles * GPX_SWEEP_TILE;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_sig = up(G * 4), b_age = up(G), b_pg = up(cap * 4), b_pa = up(cap), b_tl = up(tiles * 4);
-  char* base = nullptr;
-  int rc = dev_alloc(e, &base, b_sig + b_age + b_pg + b_pa + 4 * b_tl + 256, true);
-  if (rc != GPX_OK) return rc;
-  SweepMem& M = e->sweep;
-  char* p = base;
-  M.sig = (uint32_t*)p, p += b_sig;
-  M.age = (uint8_t*)p, p += b_age;
-  M.park_g = (int32_t*)p, p += b_pg;
-  M.park_age = (uint8_t*)p, p += b_pa;
-  M.tile_hits = (int32_t*)p, p += b_tl;
-  M.tile_nog = (int32_t*)p, p += b_tl;
-  M.tile_busy = (int32_t*)p, p += b_tl;
-  M.tile_off = (int32_t*)p, p += b_tl;
-  e->sweep_counts = (SweepCounts*)p; /* last: the marker */
-  return GPX_OK;
-}
-
-/* what needs no engine */
-int sweep_args(const gpx_engine* h, int32_t n, int32_t min_age, int32_t flags, int32_t cap, const void* o_gidx,
-               const void* o_age, const void* o_rows, const void* counts) {
-  if (!h || n < 0 || cap < 0 || !counts) return GPX_EINVAL;
-  if (min_age < 0 || min_age > 255 || (flags & ~(GPX_SWEEP_PEEK | GPX_SWEEP_HOLD))) return GPX_EINVAL;
-  if (cap > 0 && (!o_gidx || !o_age || !o_rows)) return GPX_EINVAL;
-  return GPX_OK;
-}
-/* ... and what does: the size limit, an engine an exchange kernel gave up on, the sweep's words */
-int sweep_open(gpx_engine* h, int32_t n) {
-  if ((int64_t)n > scan_max_n(h)) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  return sweep_init(h);
-}
-
-}  // namespace
+// Host-pointer side of the deactivation sweep (include/gpx_sweep.h), staged through CtlStage around gpx_pause_sweep_dev.
+// Needs: gpx_host_stage.inc (CtlStage), sweep_args (gpx_ctl_args.inc), sweep_open (gpx_sweep_dev.inc).
 
 extern "C" {
-
-int gpx_pause_sweep_dev(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t min_age, int32_t flags, int32_t cap,
-                        int32_t* o_gidx, uint8_t* o_age, gpx_hri* o_rows, gpx_sweep_counts* counts) {
-  int rc = sweep_args(h, n, min_age, flags, cap, o_gidx, o_age, o_rows, counts);
-  if (rc != GPX_OK) return rc;
-  if ((rc = sweep_open(h, n)) != GPX_OK) return rc;
-  h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n + GPX_SWEEP_TILE - 1) / GPX_SWEEP_TILE);
-  if (ntiles) LAUNCH(h, "k_sweep_tile", k_sweep_tile, ntiles, h->S, n, gidx, min_age, flags, h->sweep);
-  LAUNCH(h, "k_sweep_offsets", k_sweep_offsets, 1, (int32_t)ntiles, h->sweep, cap, flags, (SweepCounts*)counts);
-  if (ntiles && cap > 0)
-    LAUNCH(h, "k_sweep_move", k_sweep_move, ntiles, h->S, h->sweep, NameCopies{h->N.rows, (uint8_t*)h->N.tab}, cap, flags,
-           o_gidx, o_age, o_rows);
-  HIPCHK(hipGetLastError());
-  return GPX_OK;
-}
 
 int gpx_pause_sweep(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t min_age, int32_t flags, int32_t cap,
                     int32_t* o_gidx, uint8_t* o_age, gpx_hri* o_rows, gpx_sweep_counts* counts) {
   int rc = sweep_args(h, n, min_age, flags, cap, o_gidx, o_age, o_rows, counts);
   if (rc != GPX_OK) return rc;
   if ((rc = sweep_open(h, n)) != GPX_OK) return rc;
-  TmpDev t(h);
+  CtlStage t(h);
   const int32_t m = std::min(cap, n);
-  int32_t* d_g = nullptr;
-  if (gidx && n) {
-    if (!(d_g = t.get<int32_t>((size_t)n))) return GPX_ENOMEM;
-    H2D_B(d_g, gidx, (size_t)n * 4);
-  }
-  int32_t* d_og = nullptr;
-  uint8_t* d_oa = nullptr;
-  gpx_hri* d_or = nullptr;
-  if (m > 0) {
-    d_og = t.get<int32_t>((size_t)m);
-    d_oa = t.get<uint8_t>((size_t)m);
-    d_or = t.get<gpx_hri>((size_t)m);
-    if (!d_og || !d_oa || !d_or) return GPX_ENOMEM;
-  }
-  if ((rc = gpx_pause_sweep_dev(h, n, d_g, min_age, flags, m, d_og, d_oa, d_or, (gpx_sweep_counts*)h->sweep_counts)) != GPX_OK)
-    return rc;
-  D2H(counts, h->sweep_counts, sizeof(*counts));
-  HIPCHK(hipStreamSynchronize(h->sB));
+  const int32_t* d_g = n ? t.in_opt(gidx, (size_t)n) : nullptr;
+  int32_t* d_og = m > 0 ? t.out(o_gidx, (size_t)m) : nullptr;
+  uint8_t* d_oa = m > 0 ? t.out(o_age, (size_t)m) : nullptr;
+  gpx_hri* d_or = m > 0 ? t.out(o_rows, (size_t)m) : nullptr;
+  if (t.ready()) return t.rc;
+  if (t.ran(gpx_pause_sweep_dev(h, n, d_g, min_age, flags, m, d_og, d_oa, d_or, (gpx_sweep_counts*)h->sweep_counts)))
+    return t.rc;
+  t.d2h(counts, h->sweep_counts, sizeof(*counts));
+  if (t.sync()) return t.rc;
   /* the device saw min(cap, n) as its capacity; a count of hits is at most n: n_paused is already min(n_hits, cap) */
   const size_t k = (size_t)std::max(0, std::min(counts->n_hits, m));
-  if (k) {
-    D2H(o_gidx, d_og, k * 4);
-    D2H(o_age, d_oa, k);
-    D2H(o_rows, d_or, k * sizeof(gpx_hri));
-    HIPCHK(hipStreamSynchronize(h->sB));
-  }
-  return GPX_OK;
+  if (!k) return GPX_OK;
+  return t.fetch({d_og, d_oa, d_or}, k);
 }
 
 } /* extern "C" */

@@ -1,11 +1,11 @@
 """The paxosID table of the wire codec, restated, and names that attack it.  Test infrastructure only.
 
-Placement (gpx_wire_host.inc:64-76, wire_names_init; gpx_wire.hip.h:12-30, names_find / k_names_bind):
+Placement (gpx_wire_dev.inc, wire_names_init; gpx_wire.hip.h:12-30, names_find / k_names_bind):
   cap      = the smallest power of two >= 4 G, and at least 1,024 (table entries)
   buckets  = cap / 4 (128-byte buckets of four ways)
   home     = fmix32(String.hashCode) & (buckets - 1); a probe walks bucket by bucket from there and wraps to bucket 0.
 Unbinds leave tombstones; gpx_names_unbind rebuilds the table (k_names_reinsert) once the unbind requests since the
-last rebuild exceed cap / 16 (gpx_wire_host.inc:176).
+last rebuild exceed cap / 16 (gpx_names_unbind, gpx_wire_host.inc).
 
 Names: collision families (2^k names of one String.hashCode: blocks "Aa" / "BB" or a high-byte pair, which agree on
 hashCode, so all members share a home bucket whatever the placement), families behind a common prefix of >= 16 bytes

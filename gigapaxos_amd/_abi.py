@@ -169,6 +169,11 @@ _DEV_SIGS = {
     # the deactivation sweep (include/gpx_sweep.h; HIP library only: the oracle's retire / snapshot / dump are the reference)
     "pause_sweep_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
     "pause_sweep": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
+    # group images (include/gpx_image.h; HIP library only: the oracle's dump / snapshot / create are the reference)
+    "group_export_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
+    "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
+    "group_import_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP],
+    "group_import": [C.c_int32, _VP, _VP, C.c_int32, _VP],
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],
@@ -184,8 +189,10 @@ _HOST_SIGS = {
     "proposals_pack": [C.c_int32] + [_VP] * 6 + [C.c_size_t],
     "decisions_unpack": [_VP, C.c_size_t, C.c_int32] + [_VP] * 7,
     "proposals_unpack": [_VP, C.c_size_t, C.c_int32] + [_VP] * 6,
+    # include/gpx_image.h
+    "image_stride": [C.c_int32, C.c_int32],
 }
-_HOST_RESTYPES = {"packed_out_size": C.c_int64}  # every other function returns int
+_HOST_RESTYPES = {"packed_out_size": C.c_int64, "image_stride": C.c_int64}  # every other function returns int
 
 EXPORTED_SYMBOLS = (
     ["abi_version", "last_error", "engine_create"] + list(_SIGS) + list(_DEV_SIGS) + list(_HOST_SIGS)

@@ -42,6 +42,8 @@
 #include "gpx_scan.hip.h"
 #include "../../include/gpx_sweep.h"
 #include "gpx_sweep.hip.h"
+#include "../../include/gpx_image.h"
+#include "gpx_image.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -346,6 +348,13 @@ struct gpx_engine {
    * twin's counts; one zeroed block, allocated by the first sweep (sweep_counts != nullptr: the marker) */
   SweepMem sweep{};
   SweepCounts* sweep_counts = nullptr;
+  /* group images (gpx_image_dev.inc): parked entries, per-tile words, the import's row words and the host twins'
+   * counts; one block, allocated by the first export or import (img_counts != nullptr: the marker).  img_stage: the
+   * device block the host twins' rows pass through, at most img_stage_max bytes (GPX_TEST_IMAGE_STAGE=bytes: tests) */
+  ImageMem img{};
+  ImageCounts* img_counts = nullptr;
+  char* img_stage = nullptr;
+  size_t img_stage_cap = 0, img_stage_max = (size_t)64 << 20;
 };
 
 namespace {
@@ -759,6 +768,16 @@ int gpx_engine_create(const gpx_config* cfg, gpx_engine** out) {
     }
     test_counter_base = (uint32_t)v, test_counter_base_set = true;
   }
+  size_t test_image_stage = 0;
+  if (const char* is = getenv("GPX_TEST_IMAGE_STAGE")) { /* the bound of the group images' host staging (gpx_image_host.inc) */
+    char* end = nullptr;
+    const long long v = strtoll(is, &end, 10);
+    if (end == is || *end || v < 64 || v > ((long long)1 << 30)) {
+      snprintf(g_err, sizeof(g_err), "GPX_TEST_IMAGE_STAGE=%s: a byte count in [64, 2^30] is expected", is);
+      return GPX_EINVAL;
+    }
+    test_image_stage = (size_t)v;
+  }
   /* A GPU that has just been powered up (fresh box, "device(s) in a low-power state") can answer the
    * first runtime call with hipErrorNoDevice for a moment - seen once on the MI355X pool.  Wait for it, but
    * only where a ROCm driver is present at all (/dev/kfd): a host without a GPU fails at once. */
@@ -989,6 +1008,7 @@ int gpx_engine_create(const gpx_config* cfg, gpx_engine** out) {
     if (const char* tm = getenv("GPX_XCHG_TIMEOUT_MS")) e->xchg_timeout_ms = (uint32_t)std::max(1, atoi(tm));
     if (const char* sk = getenv("GPX_XCHG_TEST_SKEW")) e->xchg_test_skew = (uint32_t)std::max(0, atoi(sk));
     e->test_epoch_wrap = test_epoch_wrap;
+    if (test_image_stage) e->img_stage_max = test_image_stage;
     if (test_counter_base_set) {
       /* test switch: the cumulative counters (grid_exchange's arrivals, k_ac_small's chunk draw) start here, on the host
        * and on the device alike, so that a test can begin a few increments below 2^31 or 2^32 */
@@ -1049,6 +1069,7 @@ int gpx_engine_destroy(gpx_engine* h) {
   if (h->hs_in) HIPQ(hipHostFree(h->hs_in));
   if (h->hs_out) HIPQ(hipHostFree(h->hs_out));
   if (h->arena) HIPQ(hipFree(h->arena));
+  if (h->img_stage) HIPQ(hipFree(h->img_stage));
   for (auto& a : h->as) {
     if (a.h_cnt) HIPQ(hipHostFree(a.h_cnt));
     if (a.ev_in) HIPQ(hipEventDestroy(a.ev_in));
@@ -2373,10 +2394,12 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_elect_dev.inc"
 #include "gpx_scan_dev.inc"
 #include "gpx_sweep_dev.inc"
+#include "gpx_image_dev.inc"
 /* the control-plane host-pointer calls: CtlStage, then each family's twins over it and the public *_dev prototypes */
 #include "gpx_host_stage.inc"
 #include "gpx_wire_host.inc"
 #include "gpx_elect_host.inc"
 #include "gpx_scan_host.inc"
 #include "gpx_sweep_host.inc"
+#include "gpx_image_host.inc"
 #include "gpx_group_host.inc"

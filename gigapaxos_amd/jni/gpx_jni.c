@@ -26,6 +26,7 @@
 #include "../../include/gpx_packed.h"
 #include "../../include/gpx_scan.h"
 #include "../../include/gpx_sweep.h"
+#include "../../include/gpx_image.h"
 
 #ifdef GPX_HAVE_JNI
 #include <jni.h>
@@ -252,6 +253,18 @@ JFN(jint, pauseSweep)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint
   (void)c;
   return gpx_pause_sweep(H(h), n, B(gidx), minAge, flags, cap, B(oGidx), B(oAge), (gpx_hri*)B(oRows),
                          (gpx_sweep_counts*)B(counts));
+}
+/* group images (include/gpx_image.h): oRows / rows = a direct buffer of rows of gpx_image_stride bytes, counts = one
+ * of 16 bytes, status = one byte per row */
+JFN(jint, groupExport)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint flags, jint cap, jobject oRows,
+                       jobject counts) {
+  (void)c;
+  return gpx_group_export(H(h), n, B(gidx), flags, cap, B(oRows), (gpx_image_counts*)B(counts));
+}
+JFN(jint, groupImport)(JNIEnv* env, jclass c, jlong h, jint nRows, jobject rows, jobject gidx, jint flags,
+                       jobject status) {
+  (void)c;
+  return gpx_group_import(H(h), nRows, B(rows), B(gidx), flags, B(status));
 }
 #endif /* GPX_HAVE_JNI */
 

@@ -862,17 +862,14 @@ __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratc
   /* a bucket's outputs, group-major, as columns: decisions (six columns) or execution runs (gidx,
    * first slot, count) */
   auto put = [&](int64_t o, int32_t a, int32_t z, int32_t kd) {
-#ifdef GPX_STAGE_NT /* tuning build: the staging is not read again when the outputs are in place */
-    if (TILES && !AC) {
-      __builtin_nontemporal_store(g, &O.gidx()[o]);
-      __builtin_nontemporal_store(a, &O.slot()[o]);
-      __builtin_nontemporal_store(z, &O.median()[o]);
-      __builtin_nontemporal_store(P.my_bnum, &O.bnum()[o]);
-      __builtin_nontemporal_store(P.my_bcoord, &O.bcoord()[o]);
-      __builtin_nontemporal_store((uint8_t)kd, &O.kind()[o]);
+    /* GPX_NT_STAGE: beside the in-place columns the staging is read again only by a call that has to compact */
+    if ((GPX_NT_STREAMS & GPX_NT_STAGE) && TILES && !AC && IP.div) {
+      stream_store4<GPX_NT_STAGE>(&O.gidx()[o], g);
+      stream_store4<GPX_NT_STAGE>(&O.slot()[o], a);
+      stream_store4<GPX_NT_STAGE>(&O.median()[o], z);
+      stream_store1<GPX_NT_STAGE>(&O.kind()[o], (uint8_t)kd);
       return;
     }
-#endif
     O.gidx()[o] = g;
     O.slot()[o] = a;
     O.median()[o] = z;
@@ -895,12 +892,13 @@ __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratc
     return -1;
   };
   auto put_in_place = [&](int32_t o, int32_t a, int32_t z, int32_t kd) {
-    IP.gidx[o] = g;
-    IP.slot[o] = a;
-    IP.median[o] = z;
-    IP.bnum[o] = P.my_bnum;
-    IP.bcoord[o] = P.my_bcoord;
-    IP.kind[o] = (uint8_t)kd;
+    /* (the caller's columns: written once, read by nobody in the engine - GPX_NT_PLACE) */
+    stream_store4<GPX_NT_PLACE>(&IP.gidx[o], g);
+    stream_store4<GPX_NT_PLACE>(&IP.slot[o], a);
+    stream_store4<GPX_NT_PLACE>(&IP.median[o], z);
+    stream_store4<GPX_NT_PLACE>(&IP.bnum[o], P.my_bnum);
+    stream_store4<GPX_NT_PLACE>(&IP.bcoord[o], P.my_bcoord);
+    stream_store1<GPX_NT_PLACE>(&IP.kind[o], (uint8_t)kd);
   };
   if (in_lds) {
     VoteIter<true, AC> it;

@@ -76,6 +76,49 @@ __host__ __device__ __forceinline__ I4 mk4(int32_t x, int32_t y, int32_t z, int3
   r.w = w;
   return r;
 }
+/* Streams that the step touches ONCE - columns the caller hands in and the engine reads one time, columns it writes and
+ * never reads - marked non-temporal (`nt` on the instruction), so that in L2 and the Infinity Cache they do not stand
+ * equal, before the replacement policy, with the state and the hand-offs that the next kernel reads again.  One bit of
+ * GPX_NT_STREAMS per group of sites; a site whose bit is off compiles to the plain access.  The committed default is the
+ * set that measured faster (profiles/r16_stream_policy.txt): the vote columns are nearly all of the gain
+ * (the headline step 0.0838 -> 0.0795 ms), the two groups of output columns add about 1 % on top of them; the status
+ * prefill and the staging measured nothing, alone or in the union, and stay off.  Never for a hand-off between kernels
+ * (A.recs, A.off, A.ext), a state column or LDS. */
+#define GPX_NT_VOTES 1    /* k_scatter_tiles: the six vote columns */
+#define GPX_NT_PREFILL 2  /* k_scatter_tiles: the status prefill (off) */
+#define GPX_NT_PROPOSE 4  /* k_propose_one / k_propose_pers: the five output columns */
+#define GPX_NT_PLACE 8    /* k_bucket_ar16_tiles*: the in-place decision columns */
+#define GPX_NT_STAGE 16   /* k_bucket_ar16_tiles*: the decision staging, when the in-place columns are written too (off) */
+#ifndef GPX_NT_STREAMS
+#define GPX_NT_STREAMS (GPX_NT_VOTES | GPX_NT_PROPOSE | GPX_NT_PLACE)
+#endif
+typedef int32_t gpx_i32x4 __attribute__((ext_vector_type(4)));
+template <int BIT>
+__device__ __forceinline__ I4 stream_load16(const I4* p) {
+  if constexpr ((GPX_NT_STREAMS & BIT) != 0) {
+    const gpx_i32x4 v = __builtin_nontemporal_load((const gpx_i32x4*)p);
+    return mk4(v.x, v.y, v.z, v.w);
+  } else {
+    return *p;
+  }
+}
+template <int BIT>
+__device__ __forceinline__ int32_t stream_load4(const int32_t* p) {
+  if constexpr ((GPX_NT_STREAMS & BIT) != 0) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <int BIT, class T> /* T: a 4-byte word */
+__device__ __forceinline__ void stream_store4(T* p, T v) {
+  static_assert(sizeof(T) == 4, "stream_store4");
+  if constexpr ((GPX_NT_STREAMS & BIT) != 0) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+template <int BIT>
+__device__ __forceinline__ void stream_store1(uint8_t* p, uint8_t v) {
+  if constexpr ((GPX_NT_STREAMS & BIT) != 0) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
 /* one batch record after partitioning: exactly one 32-byte sector.
  *   accept-reply: a=slot b=acceptor c=max_cp        accept/commit: a=slot b=median_cp c=flags
  *   propose:      a=is_stop                          idx = arrival index, lg = gidx & (GB-1) */
@@ -1747,11 +1790,14 @@ struct OneRec {
   }
 };
 
-template <int KMAX, class IT>
+/* STREAM: the output columns are the caller's and nothing of this call reads them again (GPX_NT_PROPOSE: the one-record
+ * kernels of gpx_one.hip.h; the bucket path keeps the plain stores) */
+template <int KMAX, class IT, bool STREAM = false>
 __device__ __forceinline__ void apply_propose_group(
     const DevState& S, const DevScratch& X, int32_t g, IT& it, int32_t* __restrict__ o_slot,
     int32_t* __restrict__ o_bnum, int32_t* __restrict__ o_bcoord, int32_t* __restrict__ o_median,
     uint8_t* __restrict__ status, const ProposePre<KMAX>& P, const int64_t* __restrict__ handle) {
+  constexpr int NTB = STREAM ? GPX_NT_PROPOSE : 0;
   const int32_t G = S.G;
   const uint32_t gf = P.gf;
   /* not active: the proposal is kept (pre-active) but no ACCEPT goes out (PCS:254-261) */
@@ -1799,23 +1845,23 @@ __device__ __forceinline__ void apply_propose_group(
       n_drop++;
     }
     if (st != GPX_S_OK) {
-      o_slot[ix] = 0;
-      o_bnum[ix] = ob;
-      o_bcoord[ix] = oc;
-      o_median[ix] = 0;
-      status[ix] = (uint8_t)st;
+      stream_store4<NTB>(&o_slot[ix], 0);
+      stream_store4<NTB>(&o_bnum[ix], ob);
+      stream_store4<NTB>(&o_bcoord[ix], oc);
+      stream_store4<NTB>(&o_median[ix], 0);
+      stream_store1<NTB>(&status[ix], (uint8_t)st);
       continue;
     }
     const uint32_t e = PR_PRESENT | (stop ? PR_STOP : 0u);
     S.p_ring[(int64_t)(next & Wm) * G + g] = e;
     pcount++;
-    o_slot[ix] = next;
-    o_bnum[ix] = my_bnum;
-    o_bcoord[ix] = my_bcoord;
-    o_median[ix] = preparing ? 0 : median; /* getMajorityCommittedSlot: nodeSlots unchanged by propose */
+    stream_store4<NTB>(&o_slot[ix], next);
+    stream_store4<NTB>(&o_bnum[ix], my_bnum);
+    stream_store4<NTB>(&o_bcoord[ix], my_bcoord);
+    stream_store4<NTB>(&o_median[ix], preparing ? 0 : median); /* getMajorityCommittedSlot: nodeSlots unchanged by propose */
     if (preparing) {
       S.p_handle[(int64_t)(next & Wm) * G + g] = handle ? handle[ix] : 0;
-      status[ix] = GPX_S_PREACTIVE; /* over k_hist's GPX_S_OK */
+      stream_store1<NTB>(&status[ix], (uint8_t)GPX_S_PREACTIVE); /* over k_hist's GPX_S_OK */
     }
     next = (int32_t)((uint32_t)next + 1u);
     pe_prev = e;

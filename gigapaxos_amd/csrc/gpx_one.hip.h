@@ -328,12 +328,13 @@ __device__ __forceinline__ void propose_one_apply(const DevState& S, const DevSc
                                                   int32_t* __restrict__ o_bnum, int32_t* __restrict__ o_bcoord,
                                                   int32_t* __restrict__ o_median, uint8_t* __restrict__ status,
                                                   ProposePre<KMAX>& P, const int64_t* __restrict__ handle) {
+  /* (the five output columns are written once and read by nobody in the engine: GPX_NT_PROPOSE) */
   if ((uint32_t)i >= first_bad) {
-    o_slot[i] = 0;
-    o_bnum[i] = 0;
-    o_bcoord[i] = 0;
-    o_median[i] = 0;
-    status[i] = GPX_S_UNORDERED;
+    stream_store4<GPX_NT_PROPOSE>(&o_slot[i], 0);
+    stream_store4<GPX_NT_PROPOSE>(&o_bnum[i], 0);
+    stream_store4<GPX_NT_PROPOSE>(&o_bcoord[i], 0);
+    stream_store4<GPX_NT_PROPOSE>(&o_median[i], 0);
+    stream_store1<GPX_NT_PROPOSE>(&status[i], (uint8_t)GPX_S_UNORDERED);
     return;
   }
   OneRec it;
@@ -341,8 +342,9 @@ __device__ __forceinline__ void propose_one_apply(const DevState& S, const DevSc
   it.a = is_stop ? (int32_t)(is_stop[i] & 1) : 0;
   it.c = 1;
   it.done = 0;
-  status[i] = GPX_S_OK; /* no prefill pass ran; apply_propose_group overwrites it for a record it refuses */
-  apply_propose_group<KMAX, OneRec>(S, X, g, it, o_slot, o_bnum, o_bcoord, o_median, status, P, handle);
+  /* no prefill pass ran; apply_propose_group overwrites it for a record it refuses */
+  stream_store1<GPX_NT_PROPOSE>(&status[i], (uint8_t)GPX_S_OK);
+  apply_propose_group<KMAX, OneRec, true>(S, X, g, it, o_slot, o_bnum, o_bcoord, o_median, status, P, handle);
 }
 template <int KMAX>
 __global__ __launch_bounds__(GPX_BLOCK) void k_propose_one(

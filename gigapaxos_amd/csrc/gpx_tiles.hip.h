@@ -109,7 +109,6 @@ __device__ __forceinline__ void wave_majority2(int32_t x, int32_t y, int32_t m, 
  * is written back at its end, at ~6 TB/s, before the next kernel starts (MI355X_MICROARCH.md, price list: "boundary") -
  * 24 MB of sorted records were 4 us of k_scatter_tiles behind its last workgroup's exit.  (Narrower sc1 stores cost a
  * fabric write each: only for 16-byte streams.) */
-typedef int32_t gpx_i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store16_through(I4* dst, const I4 v) {
 #ifdef GPX_NO_SC1_STORES
   *dst = v;
@@ -120,15 +119,16 @@ __device__ __forceinline__ void store16_through(I4* dst, const I4 v) {
 #endif
 }
 
-/* four consecutive entries of a column; FULL: the whole vector is inside the batch (one 16-byte load) */
-template <bool FULL>
+/* four consecutive entries of a column; FULL: the whole vector is inside the batch (one 16-byte load).  NTB: GPX_NT_VOTES
+ * for the one pass over the caller's columns, 0 for a wide tile's second look at two of them (meant to hit L2). */
+template <bool FULL, int NTB = 0>
 __device__ __forceinline__ I4 tiles_load4(const int32_t* __restrict__ col, int64_t i0, int32_t n, int32_t fill) {
-  if (FULL) return *(const I4*)(col + i0);
+  if (FULL) return stream_load16<NTB>((const I4*)(col + i0));
   I4 r;
-  r.x = i0 + 0 < n ? col[i0 + 0] : fill;
-  r.y = i0 + 1 < n ? col[i0 + 1] : fill;
-  r.z = i0 + 2 < n ? col[i0 + 2] : fill;
-  r.w = i0 + 3 < n ? col[i0 + 3] : fill;
+  r.x = i0 + 0 < n ? stream_load4<NTB>(col + i0 + 0) : fill;
+  r.y = i0 + 1 < n ? stream_load4<NTB>(col + i0 + 1) : fill;
+  r.z = i0 + 2 < n ? stream_load4<NTB>(col + i0 + 2) : fill;
+  r.w = i0 + 3 < n ? stream_load4<NTB>(col + i0 + 3) : fill;
   return r;
 }
 
@@ -214,12 +214,12 @@ __device__ __forceinline__ void scatter_tile(int32_t n, int32_t G, const DevScra
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int64_t i0 = t0 + (int64_t)(k0 + u) * NT * 4 + chain;
-      g4[u] = tiles_load4<FULL>(gidx, i0, n, -1);
-      s4[u] = tiles_load4<FULL>(slot, i0, n, 0);
-      a4[u] = tiles_load4<FULL>(acceptor, i0, n, 0);
-      m4[u] = tiles_load4<FULL>(max_cp, i0, n, 0);
-      n4[u] = tiles_load4<FULL>(bnum, i0, n, 0);
-      c4[u] = tiles_load4<FULL>(bcoord, i0, n, 0);
+      g4[u] = tiles_load4<FULL, GPX_NT_VOTES>(gidx, i0, n, -1);
+      s4[u] = tiles_load4<FULL, GPX_NT_VOTES>(slot, i0, n, 0);
+      a4[u] = tiles_load4<FULL, GPX_NT_VOTES>(acceptor, i0, n, 0);
+      m4[u] = tiles_load4<FULL, GPX_NT_VOTES>(max_cp, i0, n, 0);
+      n4[u] = tiles_load4<FULL, GPX_NT_VOTES>(bnum, i0, n, 0);
+      c4[u] = tiles_load4<FULL, GPX_NT_VOTES>(bcoord, i0, n, 0);
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
@@ -260,10 +260,10 @@ __device__ __forceinline__ void scatter_tile(int32_t n, int32_t G, const DevScra
 #endif
       if (status) { /* what k_hist does for the partition path (GPX_S_OK == 0) */
         if (FULL) {
-          *(uint32_t*)(status + i0) = stw;
+          stream_store4<GPX_NT_PREFILL>((uint32_t*)(status + i0), stw);
         } else {
           for (int q = 0; q < 4; q++)
-            if (i0 + q < n) status[i0 + q] = (uint8_t)((stw >> (8 * q)) & 0xffu);
+            if (i0 + q < n) stream_store1<GPX_NT_PREFILL>(status + i0 + q, (uint8_t)((stw >> (8 * q)) & 0xffu));
         }
       }
     }

@@ -9,3 +9,4 @@ from ._abi import (  # noqa: F401
     D_DECISION, D_PREEMPTED, R_TOLOG, R_STORED, A_STOP, C_HASVALUE, C_STOP,
     F_ACCEPTS_FROM_DISK, RETIRE_PAUSE, RETIRE_KILL,
 )
+from .checkpoint import CpCounts, checkpoint_batch, checkpoint_batch_dev, CP_PEEK, CP_ADOPT, CP_MOVED  # noqa: F401,E402

@@ -65,6 +65,11 @@ class ScanCounts(C.Structure):
     _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class CpCounts(C.Structure):
+    """struct gpx_cp_counts (include/gpx_checkpoint.h)."""
+    _fields_ = [("n_adopted", C.c_int32), ("n_nogroup", C.c_int32), ("n_stopped", C.c_int32), ("n_runs", C.c_int32)]
+
+
 class SweepCounts(C.Structure):
     """struct gpx_sweep_counts (include/gpx_sweep.h)."""
     _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("n_busy", C.c_int32), ("n_paused", C.c_int32)]
@@ -174,6 +179,10 @@ _DEV_SIGS = {
     "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
     "group_import_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP],
     "group_import": [C.c_int32, _VP, _VP, C.c_int32, _VP],
+    # checkpoint transfer (include/gpx_checkpoint.h; HIP library only: the Java text, tests/checkpoint_model.py and the
+    # oracle's commit call over the skipped slots are the reference)
+    "checkpoint_batch_dev": [C.c_int32, _VP, _VP, C.c_int32] + [_VP] * 8,
+    "checkpoint_batch": [C.c_int32, _VP, _VP, C.c_int32] + [_VP] * 8,
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],

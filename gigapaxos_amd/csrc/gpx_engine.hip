@@ -42,6 +42,8 @@
 #include "gpx_scan.hip.h"
 #include "../../include/gpx_sweep.h"
 #include "gpx_sweep.hip.h"
+#include "../../include/gpx_checkpoint.h"
+#include "gpx_checkpoint.hip.h"
 #include "../../include/gpx_image.h"
 #include "gpx_image.hip.h"
 
@@ -348,6 +350,10 @@ struct gpx_engine {
    * twin's counts; one zeroed block, allocated by the first sweep (sweep_counts != nullptr: the marker) */
   SweepMem sweep{};
   SweepCounts* sweep_counts = nullptr;
+  /* checkpoint transfer (gpx_checkpoint_dev.inc): parked runs, per-tile words and the host twin's counts, inside the
+   * scans' block where that is large enough, else a block of their own (cp_counts != nullptr: the marker) */
+  CpMem cp{};
+  CpCounts* cp_counts = nullptr;
   /* group images (gpx_image_dev.inc): parked entries, per-tile words, the import's row words and the host twins'
    * counts; one block, allocated by the first export or import (img_counts != nullptr: the marker).  img_stage: the
    * device block the host twins' rows pass through, at most img_stage_max bytes (GPX_TEST_IMAGE_STAGE=bytes: tests) */
@@ -2388,13 +2394,14 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 
 } /* extern "C" */
 
-/* the *_dev calls of the wire, election, scan and sweep families: their scratch, argument checks and launches */
+/* the *_dev calls of the wire, election, scan, sweep, image and checkpoint families: their scratch, argument checks and launches */
 #include "gpx_ctl_args.inc"
 #include "gpx_wire_dev.inc"
 #include "gpx_elect_dev.inc"
 #include "gpx_scan_dev.inc"
 #include "gpx_sweep_dev.inc"
 #include "gpx_image_dev.inc"
+#include "gpx_checkpoint_dev.inc"
 /* the control-plane host-pointer calls: CtlStage, then each family's twins over it and the public *_dev prototypes */
 #include "gpx_host_stage.inc"
 #include "gpx_wire_host.inc"
@@ -2402,4 +2409,5 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_scan_host.inc"
 #include "gpx_sweep_host.inc"
 #include "gpx_image_host.inc"
+#include "gpx_checkpoint_host.inc"
 #include "gpx_group_host.inc"

@@ -27,6 +27,7 @@
 #include "../../include/gpx_scan.h"
 #include "../../include/gpx_sweep.h"
 #include "../../include/gpx_image.h"
+#include "../../include/gpx_checkpoint.h"
 
 #ifdef GPX_HAVE_JNI
 #include <jni.h>
@@ -265,6 +266,15 @@ JFN(jint, groupImport)(JNIEnv* env, jclass c, jlong h, jint nRows, jobject rows,
                        jobject status) {
   (void)c;
   return gpx_group_import(H(h), nRows, B(rows), B(gidx), flags, B(status));
+}
+/* checkpoint transfer (include/gpx_checkpoint.h): every column a direct buffer of n entries, counts = one of 16 bytes;
+ * under GPX_CP_PEEK the three run columns may be null */
+JFN(jint, checkpointBatch)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject cpSlot, jint flags,
+                           jobject oFrom, jobject oTo, jobject oFlags, jobject status, jobject xGidx, jobject xFirst,
+                           jobject xCount, jobject counts) {
+  (void)c;
+  return gpx_checkpoint_batch(H(h), n, B(gidx), B(cpSlot), flags, B(oFrom), B(oTo), B(oFlags), B(status), B(xGidx),
+                              B(xFirst), B(xCount), (gpx_cp_counts*)B(counts));
 }
 #endif /* GPX_HAVE_JNI */
 

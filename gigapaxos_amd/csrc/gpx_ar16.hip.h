@@ -38,6 +38,11 @@ struct __attribute__((aligned(16))) Vote16 {
 /* dynamic LDS the tiled per-bucket kernels may take: the CU's 160 KB less their static block (run starts and prefix of
  * up to 1024 tiles 6.1 KB, scan scratch) */
 #define GPX_TL_BUCKET_DYN_MAX (152 * 1024)
+/* the tiled per-bucket kernels stage a regular round as two words per vote and replay it in registers (bucket16_body);
+ * 0: every bucket on the four-word layout */
+#ifndef GPX_AR16_TWO_WORD
+#define GPX_AR16_TWO_WORD 1
+#endif
 
 /* staged outputs of the per-bucket kernel: six columns over the record index space (outputs of
  * bucket b at [bucket_off[b], bucket_off[b] + bucket_nout[b])) */
@@ -518,7 +523,8 @@ struct TileLds {
   __shared__ uint16_t s_st_[(TILES_) ? GPX_TL_MAXWG : 1];           \
   const TileLds TL{s_pre_, s_st_}
 /* b_in < 0: the workgroup's own bucket (blockIdx); else the bucket to do (k_bucket_ar16_tiles_pipe) */
-template <int OP, int KMAX, bool TILES = false>
+/* TWO: the kernel takes the regular round's two-word staging (GPX_AR16_TWO_WORD; the K <= 4 kernel) */
+template <int OP, int KMAX, bool TILES = false, bool TWO = false>
 __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratch& X, const Stage16& O, const VoteCols& in,
                                               const AcceptOut& R, uint8_t* __restrict__ status, const TileLds& TL,
                                               const TileArea& A = TileArea{}, int32_t b_in = -1,
@@ -539,6 +545,8 @@ __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratc
    * exclusive prefix of the run lengths, what turns a record's index in the bucket into (tile, position) */
   int32_t* const s_pre = TL.pre;
   uint16_t* const s_st = TL.st;
+  constexpr bool TW = TILES && !AC && TWO; /* the regular round's two-word staging, further down */
+  bool wide_run = false; /* TILES: one of this lane's runs of the bucket lies in a wide tile */
   if (TILES) TL_STAMP(4096 + b, 0);
   if (TILES) { /* no k_hist, no scanned offsets: rows b and b + 1 of A.off say everything */
     /* A.off is [bucket / 4][tile][4]: this bucket's start and the next one's - the same 8-byte entry three times in four */
@@ -556,6 +564,7 @@ __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratc
         const uint16_t o0 = (uint16_t)(e0 >> (16 * (b & 3))), o1 = (uint16_t)(e1 >> (16 * ((b + 1) & 3)));
         const int32_t st = (int32_t)(o0 & 0x7fffu);
         cw[q] = (int32_t)(o1 & 0x7fffu) - st;
+        wide_run = wide_run || ((o0 & TL_WIDE) && cw[q] > 0);
         s_st[w] = o0;
         ssum += st;
         csum += cw[q];
@@ -658,7 +667,11 @@ __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratc
     return tile_exp(A.recs[p], p, wide, lo);
   };
   auto tile_rec = [&](int32_t j) -> Vote16 { return tile_at(j, tile_find(j)); };
-  if (TILES) __syncthreads(); /* s_pre / s_st */
+  bool any_wide = false;
+  if (TILES) { /* s_pre / s_st */
+    if (TW) any_wide = __syncthreads_or(wide_run);
+    else __syncthreads();
+  }
   if (TILES) TL_STAMP(4096 + b, 1); /* rows of A.off read and scanned */
 #ifdef GPX_ABL_STOP /* ablation builds (wrong results): the kernel up to one of its phases */
   if (TILES && GPX_ABL_STOP == 1) return;
@@ -670,6 +683,176 @@ __device__ __forceinline__ void bucket16_body(const DevState& S, const DevScratc
     __threadfence_block();
   }
   __syncthreads();
+  /* TWO-WORD STAGING OF THE REGULAR ROUND (GPX_AR16_TWO_WORD).  A coordinator's steady state: a full bucket, every group
+   * with one to four votes that all answer its one outstanding slot at the batch's ballot, and one decision per group.  Such
+   * a bucket never expands its records: a vote of rank t goes to row t * gb + group as ONE 8-byte word pair
+   *   key = ((tile << 14 | offset in the tile) << 1) | ESC_B   orders as the arrival index does (offset < tile <= 16,384)
+   *   bw  = the record's second word as k_scatter_tiles wrote it: slot byte, checkpoint byte, acceptor
+   * over the front of the staging arrays; the group's lane reads its rows once (its own column: no bank conflicts),
+   * orders them by key in registers (a sorting network: no indexed register arrays), tests "one slot, our ballot, no
+   * escape" on the packed words, replays the votes as ar16_replay_group's straight line does - WITHOUT touching the
+   * state - and keeps its decision in registers.  ONE workgroup vote then says whether every lane got there with exactly
+   * one decision: the state is written and the outputs leave at [l] - no scan, every count is 1, the bucket's is gb.
+   * Anything else - a group with more votes than rows, an escaped slot or ballot, a higher or lower ballot, a second
+   * slot, an idle or stopped group, a group without a decision - and the WHOLE workgroup starts over below, on the
+   * four-word layout with the code that every other bucket takes: nothing was written but LDS.  A bucket that cannot be regular by what is known
+   * up front (partial, sparse, over-full, a run in a wide tile) does not try. */
+  if constexpr (TW) {
+    constexpr int KS = 4; /* rows per group */
+    static_assert(KMAX <= 4, "eight rows of two words beside the K = 5 state do not fit the kernel's registers");
+    const bool full_bucket = X.g_base + ((b + 1) << X.shift) <= X.g_end;
+    if (in_lds && KS * gb <= L && nb >= gb && nb <= KS * gb && full_bucket && !any_wide && pre) { /* (uniform) */
+      uint2* rows = (uint2*)idxA;
+      const int32_t pl = (nb + gb - 1) >> X.shift; /* records per lane, consecutive ones: <= KS */
+      const int32_t jb = l * pl, jend = min(jb + pl, nb);
+      bool bad = false;
+      auto put2 = [&](const Vote8 q, int32_t lo) {
+        const int32_t lg = (int32_t)((q.a >> 14) & 0x3ffu);
+        const int32_t t = atomicAdd(&lcnt[lg], 1);
+        if (t < KS && !(q.a & V8_ESC_S))
+          rows[t * gb + lg] = make_uint2(((((uint32_t)lo << 14) | (q.a & 0x3fffu)) << 1) | (q.a >> 31), q.b);
+        else
+          bad = true;
+      };
+      {
+        const bool v0 = jb < jend, v1 = jb + 1 < jend, v2 = jb + 2 < jend, v3 = jb + 3 < jend;
+        int32_t l0 = 0, l1 = 0, l2 = 0, l3 = 0;
+        uint32_t wd;
+        Vote8 q0{}, q1{}, q2{}, q3{};
+        /* the four places, the four loads, then what they brought (as the four-word path below) */
+        if (v0) l3 = l0 = tile_find(jb), q0 = A.recs[tile_pos(jb, l0, &wd)];
+        if (v1) l3 = l1 = tile_adv(jb + 1, l0), q1 = A.recs[tile_pos(jb + 1, l1, &wd)];
+        if (v2) l3 = l2 = tile_adv(jb + 2, l1), q2 = A.recs[tile_pos(jb + 2, l2, &wd)];
+        if (v3) l3 = tile_adv(jb + 3, l2), q3 = A.recs[tile_pos(jb + 3, l3, &wd)];
+        if (v0) put2(q0, l0);
+        if (v1) put2(q1, l1);
+        if (v2) put2(q2, l2);
+        if (v3) put2(q3, l3);
+      }
+      __syncthreads();
+      TL_STAMP(4096 + b, 3);
+      coord_preload_ring<KMAX>(S, g, P);
+      const int32_t c = lcnt[l];
+      /* the lane's rows, in named registers.  A row that holds no vote of this call orders last and is never replayed. */
+      uint32_t ky0, ky1, ky2, ky3, bw0, bw1, bw2, bw3;
+#define GPX_ROW(t)                               \
+  {                                              \
+    const uint2 r_ = rows[t * gb + l];           \
+    ky##t = t < c ? r_.x : 0xffffffffu;          \
+    bw##t = r_.y;                                \
+  }
+      GPX_ROW(0) GPX_ROW(1) GPX_ROW(2) GPX_ROW(3)
+#undef GPX_ROW
+      /* one slot, our ballot, no escape (an absent row's key is all ones: its words are masked out by t < c) */
+      bool ok = !bad && c >= 1 &&
+                (P.gf & (GF_EXISTS | GF_STOPPED | GF_HASCOORD | GF_PREPARING)) == (GF_EXISTS | GF_HASCOORD) &&
+                ref_bn == P.my_bnum && ref_bc == P.my_bcoord;
+#define GPX_CHK(t) ok = ok && (t >= c || (!(ky##t & 1u) && ((bw##t ^ bw0) & 255u) == 0));
+      GPX_CHK(0) GPX_CHK(1) GPX_CHK(2) GPX_CHK(3)
+#undef GPX_CHK
+      const int32_t s0 = slot0 + (int32_t)(bw0 & 255u) - 128;
+      {
+        const int32_t d = jsub(P.next, s0);
+        ok = ok && d >= 1 && d <= S.W;
+      }
+      /* arrival order: a sorting network over (key, word) pairs */
+#define GPX_CX(i, j)                                                                     \
+  {                                                                                      \
+    const bool sw_ = ky##i > ky##j;                                                      \
+    const uint32_t lo_ = min(ky##i, ky##j), hi_ = max(ky##i, ky##j);                     \
+    const uint32_t bl_ = sw_ ? bw##j : bw##i, bh_ = sw_ ? bw##i : bw##j;                 \
+    ky##i = lo_, ky##j = hi_, bw##i = bl_, bw##j = bh_;                                  \
+  }
+      GPX_CX(0, 1) GPX_CX(2, 3) GPX_CX(0, 2) GPX_CX(1, 3) GPX_CX(1, 2)
+#undef GPX_CX
+      /* the straight line of ar16_replay_group (handleAcceptReplyMyBallot, PCS:597-640), in registers */
+      const int32_t G = S.G, k = (int32_t)GF_K(P.gf);
+      int32_t mem[KMAX], ns[KMAX];
+#pragma unroll
+      for (int j = 0; j < KMAX; j++) {
+        mem[j] = (j < k) ? P.mem[j] : 0;
+        ns[j] = (j < k) ? P.ns[j] : 0;
+      }
+      const int64_t off = (int64_t)(s0 & (S.W - 1)) * G + g;
+      uint32_t e0 = 0;
+      if (ok) e0 = (s0 == P.pe_slot) ? P.pe : S.p_ring[off];
+      uint32_t e = e0;
+      int32_t pcount = P.pcount, ndec = 0, md = 0;
+      bool ns_dirty = false;
+      auto vote = [&](bool on, uint32_t w_) {
+        if (!on) return;
+        const int32_t acc = (int32_t)(w_ >> 16), maxcp = s0 - 1 - ((int32_t)((w_ >> 8) & 255u) - 128);
+        int32_t midx = -1;
+#pragma unroll
+        for (int q = 0; q < KMAX; q++) {
+          if (q < k && mem[q] == acc) {
+            midx = q; /* WaitforUtility.getIndex: last match */
+            if (ns[q] < maxcp) { /* recordSlotNumber :809-825 (plain <) */
+              ns[q] = maxcp;
+              ns_dirty = true;
+            }
+          }
+        }
+        if (e & PR_PRESENT) {
+          if (midx >= 0) e |= (1u << midx);   /* updateHeardFrom :51-62 */
+          if (__popc(e & 0xffffu) > k / 2) { /* heardFromMajority :64-68 */
+            md = median_minus<KMAX>(ns, k);
+            ndec++;
+            e = 0;
+            pcount--;
+          }
+        }
+      };
+      vote(0 < c, bw0), vote(1 < c, bw1), vote(2 < c, bw2), vote(3 < c, bw3);
+      ok = ok && ndec == 1;
+      if (!__syncthreads_or(!ok)) {
+        TL_STAMP(4096 + b, 4);
+        S.p_ring[off] = e; /* (a decision was made: the entry is gone) */
+        if (ns_dirty) {
+#pragma unroll
+          for (int q = 0; q < KMAX; q++)
+            if (q < k) S.node_slots[(int64_t)q * G + g] = ns[q];
+        }
+        S.c_pcount[g] = pcount;
+        /* the bucket's gb outputs, lane l's at [l]: what phase F below does with `put`, `in_place` and `put_in_place` for
+         * counts that are all 1 (same columns, same rules: the span test, the flag word, bucket_nout) */
+        const int64_t o = (int64_t)boff + l;
+        if ((GPX_NT_STREAMS & GPX_NT_STAGE) && IP.div) {
+          stream_store4<GPX_NT_STAGE>(&O.gidx()[o], g);
+          stream_store4<GPX_NT_STAGE>(&O.slot()[o], s0);
+          stream_store4<GPX_NT_STAGE>(&O.median()[o], md);
+          stream_store1<GPX_NT_STAGE>(&O.kind()[o], (uint8_t)GPX_D_DECISION);
+        } else {
+          O.gidx()[o] = g;
+          O.slot()[o] = s0;
+          O.median()[o] = md;
+          if (!IP.div) { /* (in-place form: the ballot columns are not staged) */
+            O.bnum()[o] = P.my_bnum;
+            O.bcoord()[o] = P.my_bcoord;
+          }
+          O.kind()[o] = (uint8_t)GPX_D_DECISION;
+        }
+        if (IP.div) {
+          if (gb == ip_span) {
+            const int32_t q = ip_pb + l;
+            stream_store4<GPX_NT_PLACE>(&IP.gidx[q], g);
+            stream_store4<GPX_NT_PLACE>(&IP.slot[q], s0);
+            stream_store4<GPX_NT_PLACE>(&IP.median[q], md);
+            stream_store4<GPX_NT_PLACE>(&IP.bnum[q], P.my_bnum);
+            stream_store4<GPX_NT_PLACE>(&IP.bcoord[q], P.my_bcoord);
+            stream_store1<GPX_NT_PLACE>(&IP.kind[q], (uint8_t)GPX_D_DECISION);
+          } else if (l == 0) {
+            A.ref[3] = (int32_t)X.epoch;
+          }
+        }
+        if (l == 0) X.bucket_nout[b] = gb;
+        TL_STAMP(4096 + b, 5);
+        return;
+      }
+      lcnt[l] = 0; /* start over, the general way (every lane has read its rows: the vote above was the barrier) */
+      __syncthreads();
+    }
+  }
   /* The first four votes of a lane stay in registers between its two passes (count, placement) - or its ONE pass: */
   Vote16 r0, r1, r2, r3;
   r0.meta = r1.meta = r2.meta = r3.meta = 0;
@@ -1015,17 +1198,22 @@ __device__ __forceinline__ const T& lazy_pick(const T& from_kernarg, const T& by
   if constexpr (LAZY) return from_kernarg;
   else return by_value;
 }
-#define GPX_TILES_KERNEL_BODY(KM)                                                                                          \
-  GPX_TILE_LDS_DECL(true);                                                                                                 \
-  const TilesKernArgs* ka = (const TilesKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();                                  \
-  bucket16_body<B16_AR, KM, true>(lazy_pick<(GPX_LAZY & 16) != 0>(ka->S, S), lazy_pick<(GPX_LAZY & 2) != 0>(ka->X, X), O,  \
-                                  lazy_pick<(GPX_LAZY & 1) != 0>(ka->in, in), AcceptOut{},                                 \
-                                  (GPX_LAZY & 8) ? ka->status : status, TL, lazy_pick<(GPX_LAZY & 32) != 0>(ka->A, A), -1, \
-                                  lazy_pick<(GPX_LAZY & 4) != 0>(ka->IP, IP))
+/* TWO_: the kernel takes the two-word staging of the regular round.  Its tile area then comes from the kernarg segment as
+ * well: by value, the block's four pointers stay live as ONE 8-register tuple across the new phase, and the register
+ * allocator leaves a dead 32-byte spill slot behind (private_segment_fixed_size 36 with no scratch instruction). */
+#define GPX_TILES_KERNEL_BODY(KM, TWO_)                                                                                         \
+  GPX_TILE_LDS_DECL(true);                                                                                                      \
+  constexpr bool two_ = (TWO_) && GPX_AR16_TWO_WORD != 0;                                                                       \
+  const TilesKernArgs* ka = (const TilesKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();                                       \
+  bucket16_body<B16_AR, KM, true, two_>(lazy_pick<(GPX_LAZY & 16) != 0>(ka->S, S), lazy_pick<(GPX_LAZY & 2) != 0>(ka->X, X), O, \
+                                        lazy_pick<(GPX_LAZY & 1) != 0>(ka->in, in), AcceptOut{},                                \
+                                        (GPX_LAZY & 8) ? ka->status : status, TL,                                               \
+                                        lazy_pick<(GPX_LAZY & 32) != 0 || two_>(ka->A, A), -1,                                  \
+                                        lazy_pick<(GPX_LAZY & 4) != 0>(ka->IP, IP))
 template <int KMAX>
 __global__ __launch_bounds__(1024) GPX_AR16_ATTR void k_bucket_ar16_tiles(DevState S, DevScratch X, Stage16 O, VoteCols in,
                                                                          uint8_t* __restrict__ status, TileArea A, PlaceCols IP) {
-  GPX_TILES_KERNEL_BODY(KMAX);
+  GPX_TILES_KERNEL_BODY(KMAX, false);
 }
 /* K <= 4 and five replicas held to 6 waves like k_bucket_ar16_k5 */
 #ifndef GPX_K4_WAVES
@@ -1033,11 +1221,13 @@ __global__ __launch_bounds__(1024) GPX_AR16_ATTR void k_bucket_ar16_tiles(DevSta
 #endif
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(GPX_K4_WAVES, 8))) void k_bucket_ar16_tiles_k4(
     DevState S, DevScratch X, Stage16 O, VoteCols in, uint8_t* __restrict__ status, TileArea A, PlaceCols IP) {
-  GPX_TILES_KERNEL_BODY(4);
+  GPX_TILES_KERNEL_BODY(4, true);
 }
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_bucket_ar16_tiles_k5(
     DevState S, DevScratch X, Stage16 O, VoteCols in, uint8_t* __restrict__ status, TileArea A, PlaceCols IP) {
-  GPX_TILES_KERNEL_BODY(5);
+  /* (four-word staging: eight rows of two words in registers beside the K = 5 state do not fit the 80 VGPRs of 6 waves -
+   * 32 bytes of scratch per lane when it was compiled so) */
+  GPX_TILES_KERNEL_BODY(5, false);
 }
 /* Five replicas (BASELINE config #4): the KMAX = 5 body needs 82 VGPRs left to itself - two over the step
  * to 5 waves per SIMD = two workgroups per CU instead of three; held to 6 waves it gives up two registers

@@ -661,8 +661,9 @@ __device__ __forceinline__ void cmpxchg_asc(unsigned long long* a, uint32_t lo, 
  * the whole workgroup.  All-ascending bitonic network (first stage of every merge compares t with
  * its mirror t ^ (k-1), the rest with t ^ j), so positions >= c behave as +inf simply by being
  * skipped.  A single hot group is inherently serial under the per-group ordering contract (like
- * the Java monitor); this only has to be correct.  `a` may point to LDS or to global memory. */
-__device__ void sort_long_segment(unsigned long long* a, uint32_t c) {
+ * the Java monitor); this only has to be correct.  `a` may point to LDS or to global memory.  (Forced inline, as every
+ * caller had it: left to the inliner, the two-word per-bucket kernel got it as a call, and a call needs a stack.) */
+__device__ __forceinline__ void sort_long_segment(unsigned long long* a, uint32_t c) {
   uint32_t p2 = 1;
   while (p2 < c) p2 <<= 1;
   for (uint32_t k = 2; k <= p2; k <<= 1) {

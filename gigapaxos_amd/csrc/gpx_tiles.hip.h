@@ -186,6 +186,32 @@ __device__ __forceinline__ int32_t tl_publish_starts(int32_t* cnt, int32_t* s_ws
   return tot;
 }
 
+/* GPX_TL_EARLY_LOADS (default on): round 0's six column vectors are requested BEFORE the barrier that publishes the
+ * reference vote and consumed after it - fifteen of a workgroup's sixteen waves otherwise wait there with nothing in
+ * flight, behind wave 0's load round trip and its two wave_majority2.  0: the prologue in front of every load. */
+#ifndef GPX_TL_EARLY_LOADS
+#define GPX_TL_EARLY_LOADS 1
+#endif
+/* a scatter workgroup's prologue: its bucket counters zeroed, the batch's reference vote - what most of its first 64
+ * votes carry (every tile finds the same) - in s_ref.  The caller's barrier publishes both. */
+template <int NT>
+__device__ __forceinline__ void tl_prologue(int32_t n, int32_t nbk, const TileArea& A, int32_t w, const int32_t* __restrict__ bnum,
+                                            const int32_t* __restrict__ bcoord, const int32_t* __restrict__ slot, int32_t* cnt,
+                                            int32_t* s_ref, int32_t* s_nesc) {
+  for (int32_t b = threadIdx.x; b < tl_cnt_words(nbk, NT); b += NT) cnt[b] = 0;
+  if (threadIdx.x < 64) {
+    const int32_t m = min(n, 64), i = min((int32_t)threadIdx.x, m - 1);
+    int32_t rb, rc, rs, dummy;
+    wave_majority2(bnum[i], bcoord[i], m, &rb, &rc);
+    wave_majority2(slot[i], 0, m, &rs, &dummy);
+    if (threadIdx.x == 0) {
+      s_ref[0] = rs, s_ref[1] = rb, s_ref[2] = rc;
+      *s_nesc = 0;
+      if (w == 0) A.ref[0] = rs, A.ref[1] = rb, A.ref[2] = rc;
+    }
+  }
+}
+
 #define TL_RK_MASK 0x3fffu /* rank of a vote inside its bucket's run of the tile; ESC_S / ESC_B above it (Vote8.a's bits) */
 /* FULL: every vector of the tile lies inside the batch and the status column takes 4-byte stores - every workgroup but
  * the last. */
@@ -194,23 +220,15 @@ __device__ __forceinline__ void scatter_tile(int32_t n, int32_t G, const DevScra
                                              const int32_t* __restrict__ gidx, const int32_t* __restrict__ bnum,
                                              const int32_t* __restrict__ bcoord, const int32_t* __restrict__ slot,
                                              const int32_t* __restrict__ acceptor, const int32_t* __restrict__ max_cp,
-                                             uint8_t* __restrict__ status, int32_t* cnt, Vote8* recs, const int32_t* s_ref,
+                                             uint8_t* __restrict__ status, int32_t* cnt, Vote8* recs, int32_t* s_ref,
                                              int32_t* s_nesc, int32_t* s_wsum) {
   constexpr int T = NT * 4 * R4;
   constexpr int U = (R4 == 2) ? 2 : 1; /* vectors of all six columns in flight together (R4 = 4 with two spills) */
   const int32_t nbk = X.nbk;
-  const int32_t slot0 = s_ref[0], b0n = s_ref[1], b0c = s_ref[2];
   const int32_t shift = X.shift, mask = X.gb - 1;
   const int64_t t0 = (int64_t)w * T + (int64_t)threadIdx.x * 4; /* this lane's first vector; the others NT * 4 apart */
-  /* phase 1: every column of the tile, once.  Kept per vote: the group (-1: not in the table), the packed word, the
-   * rank inside the bucket's run with the two escape bits. */
-  int32_t gg[R4 * 4];
-  uint32_t bw[R4 * 4], rk[R4 * 4];
-  int32_t bad = 0, nesc = 0;
-  int32_t chain = 0; /* always 0, but only known once the pair before has its ranks: see the end of the loop */
-#pragma unroll
-  for (int k0 = 0; k0 < R4; k0 += U) {
-    I4 g4[U], s4[U], a4[U], m4[U], n4[U], c4[U];
+  I4 g4[U], s4[U], a4[U], m4[U], n4[U], c4[U];
+  auto load_round = [&](int k0, int32_t chain) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int64_t i0 = t0 + (int64_t)(k0 + u) * NT * 4 + chain;
@@ -221,6 +239,22 @@ __device__ __forceinline__ void scatter_tile(int32_t n, int32_t G, const DevScra
       n4[u] = tiles_load4<FULL, GPX_NT_VOTES>(bnum, i0, n, 0);
       c4[u] = tiles_load4<FULL, GPX_NT_VOTES>(bcoord, i0, n, 0);
     }
+  };
+  if (GPX_TL_EARLY_LOADS) { /* round 0 in flight across the prologue and its barrier */
+    load_round(0, 0);
+    tl_prologue<NT>(n, nbk, A, w, bnum, bcoord, slot, cnt, s_ref, s_nesc);
+    __syncthreads();
+  }
+  const int32_t slot0 = s_ref[0], b0n = s_ref[1], b0c = s_ref[2];
+  /* phase 1: every column of the tile, once.  Kept per vote: the group (-1: not in the table), the packed word, the
+   * rank inside the bucket's run with the two escape bits. */
+  int32_t gg[R4 * 4];
+  uint32_t bw[R4 * 4], rk[R4 * 4];
+  int32_t bad = 0, nesc = 0;
+  int32_t chain = 0; /* always 0, but only known once the pair before has its ranks: see the end of the loop */
+#pragma unroll
+  for (int k0 = 0; k0 < R4; k0 += U) {
+    if (!GPX_TL_EARLY_LOADS || k0 > 0) load_round(k0, chain);
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const int k = k0 + u;
@@ -373,19 +407,11 @@ __global__ __launch_bounds__(NT) void k_scatter_tiles(int32_t n, int32_t G, DevS
   if (X.gate && *X.unsorted != X.epoch) return; /* a few sorted runs: k_ar_runs did it (gpx_runs.hip.h) */
   TL_STAMP(w, 0);
   TL_CLOCK(w, 6);
-  for (int32_t b = threadIdx.x; b < tl_cnt_words(nbk, NT); b += NT) cnt[b] = 0;
-  if (threadIdx.x < 64) { /* the batch's reference vote: what most of its first 64 votes carry (every tile finds the same) */
-    const int32_t m = min(n, 64), i = min((int32_t)threadIdx.x, m - 1);
-    int32_t rb, rc, rs, dummy;
-    wave_majority2(bnum[i], bcoord[i], m, &rb, &rc);
-    wave_majority2(slot[i], 0, m, &rs, &dummy);
-    if (threadIdx.x == 0) {
-      s_ref[0] = rs, s_ref[1] = rb, s_ref[2] = rc;
-      *s_nesc_p = 0;
-      if (w == 0) A.ref[0] = rs, A.ref[1] = rb, A.ref[2] = rc;
-    }
+  if (!GPX_TL_EARLY_LOADS) {
+    tl_prologue<NT>(n, nbk, A, w, bnum, bcoord, slot, cnt, s_ref, s_nesc_p);
+    __syncthreads();
   }
-  __syncthreads();
+  /* (FULL or not is known here: scatter_tile puts its first loads in front of the prologue - GPX_TL_EARLY_LOADS) */
   if ((int64_t)(w + 1) * T <= n && !((uintptr_t)status & 3))
     scatter_tile<NT, R4, true>(n, G, X, A, w, gidx, bnum, bcoord, slot, acceptor, max_cp, status, cnt, recs, s_ref, s_nesc_p, s_wsum);
   else

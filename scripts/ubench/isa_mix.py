@@ -11,7 +11,7 @@ from collections import Counter
 def main():
     text = open(sys.argv[1]).read()
     for want in sys.argv[2:]:
-        for m in re.finditer(r"^(_Z\S*" + re.escape(want) + r"\S*): +; @.*?\n(.*?)\n\ts_endpgm", text, re.S | re.M):
+        for m in re.finditer(r"^(_Z\S*" + re.escape(want) + r"\S*): +; @.*?\n(.*?)\n\.Lfunc_end", text, re.S | re.M):  # (a kernel may end in more than one place)
             ins = [ln.split()[0] for ln in m.group(2).split("\n") if ln.startswith("\t") and not ln.lstrip().startswith((".", ";"))]
             c = Counter(ins)
             valu = sum(v for k, v in c.items() if k.startswith("v_"))

@@ -20,16 +20,23 @@ INT32_MAX = (1 << 31) - 1
 
 class Pair:
     """The HIP engine and the oracle over the same table, forced onto the tiled front end (no small-call kernel) with
-    buckets of 512 groups.  base: per-group first slot (default 1 everywhere); coord: per-group coordinator."""
+    buckets of 512 groups.  base: per-group first slot (default 1 everywhere); coord: per-group coordinator.
+    node_slots: how far behind `base - 1` every member's nodeSlotNumbers entry starts (one offset per member column;
+    default 0 everywhere); window: the engine's window; tile: (votes, threads) per scatter workgroup, forced through
+    GPX_TILE_T / GPX_TILE_NT (default: chosen per call); shift: GPX_BUCKET_SHIFT (1 << shift lanes per bucket)."""
 
     def __init__(self, monkeypatch, hip_lib, oracle_lib, G=2048, k=3, members=None, kmax=None, ks=None, coord=None, base=None,
-                 holes=(), me=100):
+                 holes=(), me=100, node_slots=None, window=8, tile=None, shift=9):
         monkeypatch.setenv("GPX_SAR_MAX_N", "0")
-        monkeypatch.setenv("GPX_BUCKET_SHIFT", "9")
+        monkeypatch.setenv("GPX_BUCKET_SHIFT", str(shift))
+        if tile is not None:
+            monkeypatch.setenv("GPX_TILE_T", str(tile[0]))
+            monkeypatch.setenv("GPX_TILE_NT", str(tile[1]))
         self.G, self.k, self.me = G, k, me
+        self.W, self.tile, self.shift = window, tile, shift
         self.kmax = kmax = k if kmax is None else kmax
         self.members = list(range(100, 100 + k)) if members is None else list(members)
-        self.eh, self.eo = make_pair(hip_lib, oracle_lib, me, G, kmax, 8, max_batch=4 * G * kmax + 4096)
+        self.eh, self.eo = make_pair(hip_lib, oracle_lib, me, G, kmax, window, max_batch=4 * G * kmax + 4096)
         self.g = np.array([x for x in range(G) if x not in set(holes)], np.int32)
         n = self.g.shape[0]
         self.ks = np.full(n, k, np.uint8) if ks is None else np.asarray(ks, np.uint8)[self.g]
@@ -45,9 +52,13 @@ class Pair:
         rows["acc_gc_slot"] = wrap32(rows["acc_gc_slot"].astype(np.int64) - 1 + b)
         rows["next_proposal_slot"] = wrap32(rows["next_proposal_slot"].astype(np.int64) - 1 + b)
         rows["node_slots"][:, :kmax] = wrap32(np.repeat((b - 1)[:, None], kmax, 1)) * (np.arange(kmax)[None, :] < self.ks[:, None])
+        if node_slots is not None:
+            behind = np.asarray(node_slots, np.int64)[None, :kmax]
+            rows["node_slots"][:, :kmax] = wrap32((b - 1)[:, None] - behind) * (np.arange(kmax)[None, :] < self.ks[:, None])
         for e in (self.eh, self.eo):
             assert (e.create_groups(self.g, mem, self.ks, rows) == S_OK).all()
-        self.eh.profile(2)
+        if "profile_enable" in self.eh.lib.fn:  # (an oracle in the HIP engine's place has no kernels to name)
+            self.eh.profile(2)
         self.round = 0
 
     def propose(self, g=None):

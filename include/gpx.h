@@ -349,7 +349,11 @@ int gpx_commit_batch(gpx_engine* h, int32_t n, const int32_t* gidx, const int32_
                      int32_t* x_count, int32_t* n_runs);
 
 /* ---- data path (device pointers, asynchronous on the engine stream) ---------- */
-/* Same semantics; every pointer is device memory; n_out / n_runs are device int32. */
+/* Same semantics; every pointer is device memory; n_out / n_runs are device int32.  Alignment: int32 columns are
+ * 4-byte aligned, byte columns (is_stop, a_flags, c_kind, r_flags, d_kind, status) may lie at any address - 16-byte
+ * alignment of the columns only selects faster kernels, never another answer, and nothing outside a column's n entries
+ * is written; the calls that do refuse misaligned buffers with GPX_EINVAL say so themselves: the packed records and
+ * buffers of gpx_packed.h / gpx_packed_out.h (16 bytes) and the _dev image buffers of gpx_image.h. */
 
 int gpx_propose_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const uint8_t* is_stop,
                           int32_t* slot, int32_t* bnum, int32_t* bcoord, int32_t* median_cp,

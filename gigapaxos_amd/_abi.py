@@ -179,6 +179,11 @@ _DEV_SIGS = {
     "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
     "group_import_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP],
     "group_import": [C.c_int32, _VP, _VP, C.c_int32, _VP],
+    # delta images (include/gpx_delta.h; HIP library only: the oracle's dump is the reference)
+    "group_export_delta_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, _VP],
+    "group_export_delta": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, _VP],
+    "group_apply_delta_dev": [C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP],
+    "group_apply_delta": [C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP],
     # checkpoint transfer (include/gpx_checkpoint.h; HIP library only: the Java text, tests/checkpoint_model.py and the
     # oracle's commit call over the skipped slots are the reference)
     "checkpoint_batch_dev": [C.c_int32, _VP, _VP, C.c_int32] + [_VP] * 8,

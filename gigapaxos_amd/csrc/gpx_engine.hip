@@ -46,6 +46,8 @@
 #include "gpx_checkpoint.hip.h"
 #include "../../include/gpx_image.h"
 #include "gpx_image.hip.h"
+#include "../../include/gpx_delta.h"
+#include "gpx_delta.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -361,6 +363,10 @@ struct gpx_engine {
   ImageCounts* img_counts = nullptr;
   char* img_stage = nullptr;
   size_t img_stage_cap = 0, img_stage_max = (size_t)64 << 20;
+  /* delta images (gpx_delta_dev.inc): the marks over max_groups, parked entries, per-tile words and the host twins'
+   * counts; one zeroed block, allocated by the first delta export (delta_counts != nullptr: the marker) */
+  DeltaMem delta{};
+  DeltaCounts* delta_counts = nullptr;
 };
 
 namespace {
@@ -2401,6 +2407,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_scan_dev.inc"
 #include "gpx_sweep_dev.inc"
 #include "gpx_image_dev.inc"
+#include "gpx_delta_dev.inc"
 #include "gpx_checkpoint_dev.inc"
 /* the control-plane host-pointer calls: CtlStage, then each family's twins over it and the public *_dev prototypes */
 #include "gpx_host_stage.inc"
@@ -2409,5 +2416,6 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_scan_host.inc"
 #include "gpx_sweep_host.inc"
 #include "gpx_image_host.inc"
+#include "gpx_delta_host.inc"
 #include "gpx_checkpoint_host.inc"
 #include "gpx_group_host.inc"

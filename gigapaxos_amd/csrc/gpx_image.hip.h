@@ -213,7 +213,9 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_offsets(int32_t ntiles, Ima
   if (threadIdx.x == 0) *counts = ImageCounts{run_l, run_r, n_done, n_rows_done};
 }
 
-/* lane's words of chunk [lo, lo + CW) of the MAIN row of live group g into dst (zeroed): canonical */
+/* lane's words of chunk [lo, lo + CW) of the MAIN row of live group g into dst (zeroed): canonical.
+ * delta_sig (gpx_delta.hip.h) restates these rules and image_put_cont's word for word, to hash the words a row would
+ * hold without building it: a change here must be made there too. */
 __device__ __forceinline__ void image_put_main(const DevState& S, const ImageLayout& L, int32_t g, uint32_t gf, bool prep,
                                                int32_t lo, int32_t* __restrict__ dst) {
   const int32_t hi = lo + GPX_IMAGE_CW;
@@ -394,10 +396,13 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_move(DevState S, ImageMem M
 /* ------------------------------------------------------------------------- */
 /* import                                                                      */
 
-template <bool APPLY>
-__global__ __launch_bounds__(GPX_BLOCK) void k_image_rows(DevState S, ImageMem M, NameCopies names, ImageIdle idle,
-                                                         int32_t n_rows, const int32_t* __restrict__ rows,
-                                                         const int32_t* __restrict__ gidx, uint8_t* __restrict__ status) {
+/* The two passes of an import.  REPLACE (the delta apply, gpx_delta.hip.h): a destination that is alive is taken like a
+ * free one - the second pass writes every state word of a group either way. */
+template <bool APPLY, bool REPLACE>
+__device__ __forceinline__ void image_rows_body(const DevState& S, const ImageMem& M, const NameCopies& names,
+                                                const ImageIdle& idle, int32_t n_rows,
+                                                const int32_t* __restrict__ rows, const int32_t* __restrict__ gidx,
+                                                uint8_t* __restrict__ status) {
   __shared__ __attribute__((aligned(16))) int32_t lds[GPX_IMAGE_TILE * GPX_IMAGE_LS];
   const ImageLayout L = image_layout(S);
   const int64_t G = S.G;
@@ -422,7 +427,7 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_rows(DevState S, ImageMem M
           bad = bad || !pair;
         }
         const uint32_t dc = (d >> IMG_D_DEST_SHIFT) & 3u;
-        st = bad ? GPX_S_IMAGE : dc == 0 ? GPX_S_OK : dc == 1 ? GPX_S_NOGROUP : GPX_S_EXISTS;
+        st = bad ? GPX_S_IMAGE : (dc == 0 || (REPLACE && dc == 2)) ? GPX_S_OK : dc == 1 ? GPX_S_NOGROUP : GPX_S_EXISTS;
         kind = GPX_IMAGE_MAIN;
         dest = gidx ? gidx[row] : M.src[row];
       } else if ((d & IMG_D_CONT) && row > 0) {
@@ -430,7 +435,7 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_rows(DevState S, ImageMem M
         if ((d0 & IMG_D_MAIN) && (d0 & IMG_D_CONTINUED) && M.src[row - 1] == M.src[row]) {
           const bool bad = ((d0 | d) & IMG_D_BAD) != 0;
           const uint32_t dc = (d0 >> IMG_D_DEST_SHIFT) & 3u;
-          st = bad ? GPX_S_IMAGE : dc == 0 ? GPX_S_OK : dc == 1 ? GPX_S_NOGROUP : GPX_S_EXISTS;
+          st = bad ? GPX_S_IMAGE : (dc == 0 || (REPLACE && dc == 2)) ? GPX_S_OK : dc == 1 ? GPX_S_NOGROUP : GPX_S_EXISTS;
           kind = GPX_IMAGE_CONT;
           dest = gidx ? gidx[row - 1] : M.src[row - 1];
         }
@@ -648,4 +653,11 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_rows(DevState S, ImageMem M
       idle.age[dest] = 0;
     }
   }
+}
+
+template <bool APPLY>
+__global__ __launch_bounds__(GPX_BLOCK) void k_image_rows(DevState S, ImageMem M, NameCopies names, ImageIdle idle,
+                                                         int32_t n_rows, const int32_t* __restrict__ rows,
+                                                         const int32_t* __restrict__ gidx, uint8_t* __restrict__ status) {
+  image_rows_body<APPLY, false>(S, M, names, idle, n_rows, rows, gidx, status);
 }

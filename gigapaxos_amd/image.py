@@ -4,7 +4,10 @@
 device addresses (0 = NULL) and queue the call on the engine's stream.  `rows_to_dumps` turns rows into the canonical
 words of gpx_group_dump, `move_groups` takes live groups from one engine to another through device memory.  The
 signatures are registered in `_abi._DEV_SIGS` / `_HOST_SIGS` (HIP library only: the CPU oracle's group_dump,
-group_snapshot and group_create are the specification of these)."""
+group_snapshot and group_create are the specification of these).
+
+Delta images (include/gpx_delta.h): `export_delta` / `apply_delta` and their `_dev` forms move only the groups that
+changed since the export that last wrote them; `mirror_groups` keeps a second engine current through device memory."""
 from __future__ import annotations
 
 import ctypes as C
@@ -219,3 +222,113 @@ def move_groups(src: Engine, dst: Engine, src_gidx, dst_gidx):
     res = torch.full((n,), S_NOGROUP, dtype=torch.uint8, device=dev)
     res[entry[main]] = status[main]
     return res.cpu().numpy()
+
+
+# ---- delta images (include/gpx_delta.h) ----
+DELTA_EVICT, DELTA_FULL = 1, 2
+DELTA_COUNTS_BYTES = 32
+
+
+class DeltaCounts(C.Structure):
+    """struct gpx_delta_counts (include/gpx_delta.h)."""
+    _fields_ = [(f, C.c_int32) for f in ("n_live", "n_changed", "n_rows", "n_done", "n_rows_done", "n_gone", "n_gone_done",
+                                         "reserved")]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+def export_delta(e: Engine, gidx=None, flags=0, cap=None, cap_gone=None, n=None, out=None, out_gone=None):
+    """gpx_group_export_delta: (rows written as uint8 [n_rows_done, stride], the gone groups as int32 [n_gone_done],
+    DeltaCounts).  gidx None = groups 0 .. n-1 (n None: the whole table).  cap / cap_gone None = whatever the entries
+    need (one counting call first, which changes no mark); `out` / `out_gone`: contiguous arrays (uint8 of at least
+    cap * stride bytes, int32 of at least cap_gone entries) to write into instead of fresh ones; a cap of 0 without its
+    array passes a null buffer."""
+    if gidx is None:
+        n, g = (int(e.cfg.max_groups) if n is None else int(n)), None
+    else:
+        g = _i32(gidx)
+        n = g.shape[0]
+    stride = _stride(e)
+    counts = DeltaCounts()
+    fn = e.lib.fn["group_export_delta"]
+    if cap is None or cap_gone is None:
+        e.lib.check(fn(e.h, n, _p(g), int(flags) & DELTA_FULL, 0, None, 0, None, C.byref(counts)), "group_export_delta")
+        cap = int(counts.n_rows) if cap is None else cap
+        cap_gone = int(counts.n_gone) if cap_gone is None else cap_gone
+    cap, cap_gone = int(cap), int(cap_gone)
+    if out is None:
+        out = np.zeros(cap * stride, np.uint8) if cap else None
+    elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < cap * stride:
+        raise ValueError("out: a contiguous uint8 array of at least cap * stride bytes")
+    if out_gone is None:
+        out_gone = np.zeros(cap_gone, np.int32) if cap_gone else None
+    elif out_gone.dtype != np.int32 or not out_gone.flags.c_contiguous or out_gone.size < cap_gone:
+        raise ValueError("out_gone: a contiguous int32 array of at least cap_gone entries")
+    e.lib.check(fn(e.h, n, _p(g), int(flags), cap, _p(out), cap_gone, _p(out_gone), C.byref(counts)), "group_export_delta")
+    k = int(counts.n_rows_done)
+    rows = np.zeros((0, stride), np.uint8) if out is None else out.reshape(-1)[:k * stride].reshape(k, stride)
+    gone = np.zeros(0, np.int32) if out_gone is None else out_gone.reshape(-1)[:int(counts.n_gone_done)]
+    return rows, gone, counts
+
+
+def apply_delta(e: Engine, rows, gidx=None, flags=0, gone=None):
+    """gpx_group_apply_delta: (the status of every row, the status of every gone entry).  rows: uint8 [n_rows, stride]
+    (or flat, or None); gidx None = every group goes to its source gidx."""
+    stride = _stride(e)
+    rows = np.zeros((0, stride), np.uint8) if rows is None else np.ascontiguousarray(rows).view(np.uint8).reshape(-1, stride)
+    n = rows.shape[0]
+    g = None if gidx is None else _i32(gidx, n)
+    x = _i32([] if gone is None else gone)
+    status, gstatus = np.zeros(max(n, 1), np.uint8), np.zeros(max(x.shape[0], 1), np.uint8)
+    e.lib.check(e.lib.fn["group_apply_delta"](e.h, n, _p(rows) if n else None, _p(g), int(flags), _p(status), x.shape[0],
+                                              _p(x) if x.shape[0] else None, _p(gstatus)), "group_apply_delta")
+    return status[:n], gstatus[:x.shape[0]]
+
+
+def export_delta_dev(e: Engine, n, gidx_ptr, flags, cap, rows_ptr, cap_gone, gone_ptr, counts_ptr):
+    """gpx_group_export_delta_dev: the pointers are integer device addresses (0 = NULL).  Asynchronous."""
+    e.lib.check(e.lib.fn["group_export_delta_dev"](e.h, int(n), _v(gidx_ptr), int(flags), int(cap), _v(rows_ptr), int(cap_gone),
+                                                   _v(gone_ptr), _v(counts_ptr)), "group_export_delta_dev")
+
+
+def apply_delta_dev(e: Engine, n_rows, rows_ptr, gidx_ptr, flags, status_ptr, n_gone, gone_ptr, gone_status_ptr):
+    """gpx_group_apply_delta_dev: the pointers are integer device addresses (0 = NULL).  Asynchronous."""
+    e.lib.check(e.lib.fn["group_apply_delta_dev"](e.h, int(n_rows), _v(rows_ptr), _v(gidx_ptr), int(flags), _v(status_ptr),
+                                                  int(n_gone), _v(gone_ptr), _v(gone_status_ptr)), "group_apply_delta_dev")
+
+
+def mirror_groups(src: Engine, dst: Engine, full=False):
+    """Brings `dst` up to date with `src` over the whole table: one delta export on `src` (a baseline under `full`), one
+    apply on `dst` at the same rows, through device buffers - only the counts and the status bytes cross the link.
+    Both engines live on the current device and have the same max_groups, kmax, window and my_id.  The host must not
+    feed `dst` groups that `src` owns.  Returns (DeltaCounts of the export, row statuses, gone statuses)."""
+    import torch
+
+    stride = _stride(src)
+    if _stride(dst) != stride or int(dst.cfg.max_groups) != int(src.cfg.max_groups):
+        raise ValueError("mirror_groups: the engines differ in max_groups, kmax or window")
+    n = int(src.cfg.max_groups)
+    dev = "cuda"
+    cnt = torch.zeros(8, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    fl = DELTA_FULL if full else 0
+    export_delta_dev(src, n, 0, fl, 0, 0, 0, 0, cnt.data_ptr())          # count: changes no mark
+    src.sync()
+    c = cnt.cpu().tolist()
+    n_rows, n_gone = c[2], c[5]
+    rows = torch.empty((max(n_rows, 1), stride // 4), dtype=torch.int32, device=dev)
+    gone = torch.empty(max(n_gone, 1), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    export_delta_dev(src, n, 0, fl, n_rows, rows.data_ptr() if n_rows else 0, n_gone, gone.data_ptr() if n_gone else 0,
+                     cnt.data_ptr())
+    src.sync()
+    counts = DeltaCounts(*cnt.cpu().tolist())
+    assert counts.n_rows_done == n_rows and counts.n_gone_done == n_gone
+    status = torch.zeros(max(n_rows, 1), dtype=torch.uint8, device=dev)
+    gstatus = torch.zeros(max(n_gone, 1), dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    apply_delta_dev(dst, n_rows, rows.data_ptr() if n_rows else 0, 0, IMG_VIEWCHANGE if n_rows > counts.n_done else 0,
+                    status.data_ptr(), n_gone, gone.data_ptr() if n_gone else 0, gstatus.data_ptr())
+    dst.sync()
+    return counts, status[:n_rows].cpu().numpy(), gstatus[:n_gone].cpu().numpy()

@@ -27,6 +27,7 @@
 #include "../../include/gpx_scan.h"
 #include "../../include/gpx_sweep.h"
 #include "../../include/gpx_image.h"
+#include "../../include/gpx_delta.h"
 #include "../../include/gpx_checkpoint.h"
 
 #ifdef GPX_HAVE_JNI
@@ -266,6 +267,18 @@ JFN(jint, groupImport)(JNIEnv* env, jclass c, jlong h, jint nRows, jobject rows,
                        jobject status) {
   (void)c;
   return gpx_group_import(H(h), nRows, B(rows), B(gidx), flags, B(status));
+}
+/* delta images (include/gpx_delta.h): rows as above, oGone / gone = direct buffers of 32-bit group numbers, counts =
+ * one of 32 bytes, status / goneStatus = one byte per row / per gone entry */
+JFN(jint, exportDelta)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint flags, jint cap, jobject oRows,
+                       jint capGone, jobject oGone, jobject counts) {
+  (void)c;
+  return gpx_group_export_delta(H(h), n, B(gidx), flags, cap, B(oRows), capGone, B(oGone), (gpx_delta_counts*)B(counts));
+}
+JFN(jint, applyDelta)(JNIEnv* env, jclass c, jlong h, jint nRows, jobject rows, jobject gidx, jint flags, jobject status,
+                      jint nGone, jobject gone, jobject goneStatus) {
+  (void)c;
+  return gpx_group_apply_delta(H(h), nRows, B(rows), B(gidx), flags, B(status), nGone, B(gone), B(goneStatus));
 }
 /* checkpoint transfer (include/gpx_checkpoint.h): every column a direct buffer of n entries, counts = one of 16 bytes;
  * under GPX_CP_PEEK the three run columns may be null */

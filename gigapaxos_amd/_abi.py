@@ -75,6 +75,19 @@ class SweepCounts(C.Structure):
     _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("n_busy", C.c_int32), ("n_paused", C.c_int32)]
 
 
+RTX_MAX_STEPS = 32
+
+
+class RtxCfg(C.Structure):
+    """struct gpx_rtx_cfg (include/gpx_timers.h): host memory, passed by pointer."""
+    _fields_ = [("n_steps", C.c_int32), ("accept_ms", C.c_int32 * RTX_MAX_STEPS), ("prepare_ms", C.c_int32 * RTX_MAX_STEPS)]
+
+
+class RtxCounts(C.Structure):
+    """struct gpx_rtx_counts (include/gpx_timers.h)."""
+    _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("n_waiting", C.c_int32), ("n_fired", C.c_int32)]
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -174,6 +187,10 @@ _DEV_SIGS = {
     # the deactivation sweep (include/gpx_sweep.h; HIP library only: the oracle's retire / snapshot / dump are the reference)
     "pause_sweep_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
     "pause_sweep": [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
+    # the retransmission sweep (include/gpx_timers.h; HIP library only: the oracle's poke_scan and tests/timers_model.py
+    # are the reference)
+    "retransmit_sweep_dev": [C.c_int32, _VP, C.c_int32, C.POINTER(RtxCfg), C.c_int32, C.c_int32] + [_VP] * 11,
+    "retransmit_sweep": [C.c_int32, _VP, C.c_int32, C.POINTER(RtxCfg), C.c_int32, C.c_int32] + [_VP] * 11,
     # group images (include/gpx_image.h; HIP library only: the oracle's dump / snapshot / create are the reference)
     "group_export_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
     "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
@@ -205,6 +222,8 @@ _HOST_SIGS = {
     "proposals_unpack": [_VP, C.c_size_t, C.c_int32] + [_VP] * 6,
     # include/gpx_image.h
     "image_stride": [C.c_int32, C.c_int32],
+    # include/gpx_timers.h
+    "rtx_backoff_table": [C.c_int32, C.c_double, C.c_int32, _VP],
 }
 _HOST_RESTYPES = {"packed_out_size": C.c_int64, "image_stride": C.c_int64}  # every other function returns int
 

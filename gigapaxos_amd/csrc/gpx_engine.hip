@@ -42,6 +42,8 @@
 #include "gpx_scan.hip.h"
 #include "../../include/gpx_sweep.h"
 #include "gpx_sweep.hip.h"
+#include "../../include/gpx_timers.h"
+#include "gpx_timers.hip.h"
 #include "../../include/gpx_checkpoint.h"
 #include "gpx_checkpoint.hip.h"
 #include "../../include/gpx_image.h"
@@ -352,6 +354,10 @@ struct gpx_engine {
    * twin's counts; one zeroed block, allocated by the first sweep (sweep_counts != nullptr: the marker) */
   SweepMem sweep{};
   SweepCounts* sweep_counts = nullptr;
+  /* retransmission sweep (gpx_timers_dev.inc): timer words over max_groups, parked hits, per-tile words and the host
+   * twin's counts; one zeroed block, allocated by the first such sweep (rtx_counts != nullptr: the marker) */
+  RtxMem rtx{};
+  RtxCounts* rtx_counts = nullptr;
   /* checkpoint transfer (gpx_checkpoint_dev.inc): parked runs, per-tile words and the host twin's counts, inside the
    * scans' block where that is large enough, else a block of their own (cp_counts != nullptr: the marker) */
   CpMem cp{};
@@ -2400,12 +2406,13 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 
 } /* extern "C" */
 
-/* the *_dev calls of the wire, election, scan, sweep, image and checkpoint families: their scratch, argument checks and launches */
+/* the *_dev calls of the wire, election, scan, sweep, timer, image and checkpoint families: their scratch, argument checks and launches */
 #include "gpx_ctl_args.inc"
 #include "gpx_wire_dev.inc"
 #include "gpx_elect_dev.inc"
 #include "gpx_scan_dev.inc"
 #include "gpx_sweep_dev.inc"
+#include "gpx_timers_dev.inc"
 #include "gpx_image_dev.inc"
 #include "gpx_delta_dev.inc"
 #include "gpx_checkpoint_dev.inc"
@@ -2415,6 +2422,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_elect_host.inc"
 #include "gpx_scan_host.inc"
 #include "gpx_sweep_host.inc"
+#include "gpx_timers_host.inc"
 #include "gpx_image_host.inc"
 #include "gpx_delta_host.inc"
 #include "gpx_checkpoint_host.inc"

@@ -26,6 +26,7 @@
 #include "../../include/gpx_packed.h"
 #include "../../include/gpx_scan.h"
 #include "../../include/gpx_sweep.h"
+#include "../../include/gpx_timers.h"
 #include "../../include/gpx_image.h"
 #include "../../include/gpx_delta.h"
 #include "../../include/gpx_checkpoint.h"
@@ -255,6 +256,17 @@ JFN(jint, pauseSweep)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint
   (void)c;
   return gpx_pause_sweep(H(h), n, B(gidx), minAge, flags, cap, B(oGidx), B(oAge), (gpx_hri*)B(oRows),
                          (gpx_sweep_counts*)B(counts));
+}
+/* the retransmission sweep (include/gpx_timers.h): cfg = a direct buffer of 260 bytes (the step count, then the two
+ * tables of 32 thresholds), the ten output columns direct buffers of cap entries, counts = one of 16 bytes */
+JFN(jint, retransmitSweep)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jint nowMs, jobject cfg, jint flags,
+                           jint cap, jobject oGidx, jobject oPoke, jobject oSlot, jobject oBnum, jobject oBcoord,
+                           jobject oMedianCp, jobject oFlags, jobject oHeard, jobject oCount, jobject oWaited,
+                           jobject counts) {
+  (void)c;
+  return gpx_retransmit_sweep(H(h), n, B(gidx), nowMs, (const gpx_rtx_cfg*)B(cfg), flags, cap, B(oGidx), B(oPoke),
+                              B(oSlot), B(oBnum), B(oBcoord), B(oMedianCp), B(oFlags), B(oHeard), B(oCount), B(oWaited),
+                              (gpx_rtx_counts*)B(counts));
 }
 /* group images (include/gpx_image.h): oRows / rows = a direct buffer of rows of gpx_image_stride bytes, counts = one
  * of 16 bytes, status = one byte per row */

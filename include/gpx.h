@@ -562,6 +562,7 @@ int gpx_prepare_reply_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, c
  * heard = waitforMyBallot's mask} iff a coordinator exists and is not active.  The clocks stay with
  * the host (testAndSetWaitingTooLong's ACCEPT_TIMEOUT / PREPARE_TIMEOUT with exponential backoff, PCS:
  * 715-739): it calls this for the groups whose batch timer expired.  No state changes.  Host pointers.
+ * (gpx_retransmit_sweep, include/gpx_timers.h, keeps those clocks on the device and returns only the due rows.)
  */
 int gpx_poke_scan(gpx_engine* h, int32_t n, const int32_t* gidx, uint8_t* poke, int32_t* slot,
                   int32_t* bnum, int32_t* bcoord, int32_t* median_cp, uint8_t* p_flags,

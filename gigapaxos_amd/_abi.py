@@ -88,6 +88,12 @@ class RtxCounts(C.Structure):
     _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("n_waiting", C.c_int32), ("n_fired", C.c_int32)]
 
 
+class JournalCounts(C.Structure):
+    """struct gpx_journal_counts (include/gpx_journal.h): 32 bytes."""
+    _fields_ = [("n_entries", C.c_int32), ("n_done", C.c_int32), ("n_bad", C.c_int32), ("reserved", C.c_int32),
+                ("n_bytes", C.c_int64), ("bytes_done", C.c_int64)]
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -124,6 +130,10 @@ assert HRI_DTYPE.itemsize == 4 * (9 + KMAX_LIMIT)
 _I32P = C.POINTER(C.c_int32)
 _U8P = C.POINTER(C.c_uint8)
 _VP = C.c_void_p
+# gpx_journal_pack[_dev] after the handle: n, frames, frames_bytes, n_frames, the nine input columns, base_offset, flags,
+# out, cap_bytes, cap_entries, the seven row columns, counts
+_JOURNAL_PACK_ARGS = ([C.c_int32, _VP, C.c_int64, C.c_int32] + [_VP] * 9 + [C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int32]
+                      + [_VP] * 8)
 
 # name -> argtypes (after the engine handle); every function returns int
 _SIGS = {
@@ -191,6 +201,10 @@ _DEV_SIGS = {
     # are the reference)
     "retransmit_sweep_dev": [C.c_int32, _VP, C.c_int32, C.POINTER(RtxCfg), C.c_int32, C.c_int32] + [_VP] * 11,
     "retransmit_sweep": [C.c_int32, _VP, C.c_int32, C.POINTER(RtxCfg), C.c_int32, C.c_int32] + [_VP] * 11,
+    # journal batches (include/gpx_journal.h; HIP library only: tests/journal_model.py and FileLogger::logBatch are the
+    # reference)
+    "journal_pack_dev": _JOURNAL_PACK_ARGS,
+    "journal_pack": _JOURNAL_PACK_ARGS,
     # group images (include/gpx_image.h; HIP library only: the oracle's dump / snapshot / create are the reference)
     "group_export_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
     "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
@@ -224,6 +238,8 @@ _HOST_SIGS = {
     "image_stride": [C.c_int32, C.c_int32],
     # include/gpx_timers.h
     "rtx_backoff_table": [C.c_int32, C.c_double, C.c_int32, _VP],
+    # include/gpx_journal.h
+    "journal_walk": [_VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP],
 }
 _HOST_RESTYPES = {"packed_out_size": C.c_int64, "image_stride": C.c_int64}  # every other function returns int
 

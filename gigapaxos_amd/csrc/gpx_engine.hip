@@ -44,6 +44,8 @@
 #include "gpx_sweep.hip.h"
 #include "../../include/gpx_timers.h"
 #include "gpx_timers.hip.h"
+#include "../../include/gpx_journal.h"
+#include "gpx_journal.hip.h"
 #include "../../include/gpx_checkpoint.h"
 #include "gpx_checkpoint.hip.h"
 #include "../../include/gpx_image.h"
@@ -358,6 +360,12 @@ struct gpx_engine {
    * twin's counts; one zeroed block, allocated by the first such sweep (rtx_counts != nullptr: the marker) */
   RtxMem rtx{};
   RtxCounts* rtx_counts = nullptr;
+  /* journal batches (gpx_journal_dev.inc): per-tile words, one descriptor per record of the largest batch and the host
+   * twin's counts; one block, allocated by the first such call (jr_counts != nullptr: the marker).  jr_stage_max: the
+   * window of frame bytes one chunk of the host twin copies in (GPX_TEST_JOURNAL_STAGE=bytes at that first call: tests) */
+  JrMem jr{};
+  JrCounts* jr_counts = nullptr;
+  size_t jr_stage_max = (size_t)64 << 20;
   /* checkpoint transfer (gpx_checkpoint_dev.inc): parked runs, per-tile words and the host twin's counts, inside the
    * scans' block where that is large enough, else a block of their own (cp_counts != nullptr: the marker) */
   CpMem cp{};
@@ -2406,13 +2414,14 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 
 } /* extern "C" */
 
-/* the *_dev calls of the wire, election, scan, sweep, timer, image and checkpoint families: their scratch, argument checks and launches */
+/* the *_dev calls of the wire, election, scan, sweep, timer, journal, image and checkpoint families: their scratch, argument checks and launches */
 #include "gpx_ctl_args.inc"
 #include "gpx_wire_dev.inc"
 #include "gpx_elect_dev.inc"
 #include "gpx_scan_dev.inc"
 #include "gpx_sweep_dev.inc"
 #include "gpx_timers_dev.inc"
+#include "gpx_journal_dev.inc"
 #include "gpx_image_dev.inc"
 #include "gpx_delta_dev.inc"
 #include "gpx_checkpoint_dev.inc"
@@ -2423,6 +2432,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_scan_host.inc"
 #include "gpx_sweep_host.inc"
 #include "gpx_timers_host.inc"
+#include "gpx_journal_host.inc"
 #include "gpx_image_host.inc"
 #include "gpx_delta_host.inc"
 #include "gpx_checkpoint_host.inc"

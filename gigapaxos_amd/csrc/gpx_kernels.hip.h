@@ -89,8 +89,10 @@ __host__ __device__ __forceinline__ I4 mk4(int32_t x, int32_t y, int32_t z, int3
 #define GPX_NT_PROPOSE 4  /* k_propose_one / k_propose_pers: the five output columns */
 #define GPX_NT_PLACE 8    /* k_bucket_ar16_tiles*: the in-place decision columns */
 #define GPX_NT_STAGE 16   /* k_bucket_ar16_tiles*: the decision staging, when the in-place columns are written too (off) */
+#define GPX_NT_JOURNAL 32 /* k_jr_copy (gpx_journal.hip.h): the frame bytes it reads and the journal bytes it writes (on by
+                           * the rule above - touched once; not measured against the plain form) */
 #ifndef GPX_NT_STREAMS
-#define GPX_NT_STREAMS (GPX_NT_VOTES | GPX_NT_PROPOSE | GPX_NT_PLACE)
+#define GPX_NT_STREAMS (GPX_NT_VOTES | GPX_NT_PROPOSE | GPX_NT_PLACE | GPX_NT_JOURNAL)
 #endif
 typedef int32_t gpx_i32x4 __attribute__((ext_vector_type(4)));
 template <int BIT>
@@ -112,6 +114,16 @@ __device__ __forceinline__ void stream_store4(T* p, T v) {
   static_assert(sizeof(T) == 4, "stream_store4");
   if constexpr ((GPX_NT_STREAMS & BIT) != 0) __builtin_nontemporal_store(v, p);
   else *p = v;
+}
+template <int BIT>
+__device__ __forceinline__ void stream_store16(I4* p, I4 v) {
+  if constexpr ((GPX_NT_STREAMS & BIT) != 0) {
+    gpx_i32x4 q;
+    q.x = v.x, q.y = v.y, q.z = v.z, q.w = v.w;
+    __builtin_nontemporal_store(q, (gpx_i32x4*)p);
+  } else {
+    *p = v;
+  }
 }
 template <int BIT>
 __device__ __forceinline__ void stream_store1(uint8_t* p, uint8_t v) {

@@ -27,6 +27,7 @@
 #include "../../include/gpx_scan.h"
 #include "../../include/gpx_sweep.h"
 #include "../../include/gpx_timers.h"
+#include "../../include/gpx_journal.h"
 #include "../../include/gpx_image.h"
 #include "../../include/gpx_delta.h"
 #include "../../include/gpx_checkpoint.h"
@@ -267,6 +268,21 @@ JFN(jint, retransmitSweep)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx,
   return gpx_retransmit_sweep(H(h), n, B(gidx), nowMs, (const gpx_rtx_cfg*)B(cfg), flags, cap, B(oGidx), B(oPoke),
                               B(oSlot), B(oBnum), B(oBcoord), B(oMedianCp), B(oFlags), B(oHeard), B(oCount), B(oWaited),
                               (gpx_rtx_counts*)B(counts));
+}
+/* journal batches (include/gpx_journal.h): frames = a direct buffer of framesBytes bytes, the columns direct buffers of n
+ * entries (frameLen and recFrame may be null), out = a direct buffer of capBytes bytes at a 16-byte boundary, the seven
+ * row columns direct buffers of capEntries entries (the first five may be null), counts = one of 32 bytes.  The caller
+ * writes out[0, bytesDone) to the log file with one write and keeps the call's replies until that write is durable */
+JFN(jint, journalPack)(JNIEnv* env, jclass c, jlong h, jint n, jobject frames, jlong framesBytes, jint nFrames,
+                       jobject frameOff, jobject frameLen, jobject recFrame, jobject gidx, jobject slot, jobject bnum,
+                       jobject bcoord, jobject rFlags, jobject status, jlong baseOffset, jint flags, jobject out,
+                       jlong capBytes, jint capEntries, jobject eRec, jobject eGidx, jobject eSlot, jobject eBnum,
+                       jobject eBcoord, jobject eOff, jobject eLen, jobject counts) {
+  (void)c;
+  return gpx_journal_pack(H(h), n, B(frames), framesBytes, nFrames, B(frameOff), B(frameLen), B(recFrame), B(gidx),
+                          B(slot), B(bnum), B(bcoord), B(rFlags), B(status), baseOffset, flags, B(out), capBytes,
+                          capEntries, B(eRec), B(eGidx), B(eSlot), B(eBnum), B(eBcoord), B(eOff), B(eLen),
+                          (gpx_journal_counts*)B(counts));
 }
 /* group images (include/gpx_image.h): oRows / rows = a direct buffer of rows of gpx_image_stride bytes, counts = one
  * of 16 bytes, status = one byte per row */

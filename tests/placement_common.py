@@ -303,7 +303,153 @@ class Placer:
                          r["d_kind"][:m], r.get("status"))
 
 
-class PlacedDevEngine(Placer, DevEngine):
+# ---- the view change's entry points (gpx_election_begin, gpx_prepare_reply_batch) ------------------------------------------
+# Their columns do not all have n entries: pv_off has n + 1, the five pvalue columns pv_off[n], the four list outputs
+# `window` planes of n entries each (entry j of record i at [j * n + i]); pv_handle and e_handle are 64-bit.
+ELECT_OPS = {
+    "election_begin": ("election_begin", [("gidx", 4), ("bnum", 4)], [("e_status", 1)]),
+    "prepare_reply": ("prepare_reply_batch",
+                      [("gidx", 4), ("acceptor", 4), ("r_bnum", 4), ("r_bcoord", 4), ("first_slot", 4), ("pv_off", 4), ("pv_slot", 4),
+                       ("pv_bnum", 4), ("pv_bcoord", 4), ("pv_handle", 8), ("pv_flags", 1)],
+                      [("v_kind", 1), ("e_count", 4), ("e_median", 4), ("e_slot", 4), ("e_kind", 1), ("e_handle", 8), ("e_flags", 1),
+                       ("status", 1)]),
+}
+ELECT_PLANES = ("e_slot", "e_kind", "e_handle", "e_flags")
+ELECT_ENTRY_POINTS = tuple(ELECT_OPS)
+
+
+class WideColumn(Column):
+    """A column of 1-, 4- or 8-byte entries."""
+
+    def dtype(self):
+        return {1: np.uint8, 4: np.int32, 8: np.int64}[self.width]
+
+
+def elect_poison(op, arrays):
+    """(front, behind) for the view change's input columns.  Behind the record columns: further replies - record
+    n - 1 - 7 j with the acceptor of the record after it (in most cases a member that has not answered yet: the reply
+    would count) - with empty slices (pv_off goes on at pv_off[n]); in front the same from record 0 on.  Around the
+    pvalue columns: the column's own entries again, one ballot number higher, other handles, the stop flag set - a slice
+    read too far carries them over in place of what the group accepted."""
+    n = arrays[0].shape[0]
+    j = np.arange(P)
+    src_b, src_f = (n - 1 - 7 * j) % n, (7 * (P - 1 - j)) % n
+    front, behind = [], []
+    names = [nm for nm, _ in ELECT_OPS[op][1]]
+    for nm, a in zip(names, arrays):
+        if nm == "pv_off":
+            front.append(np.zeros(P, np.int32)), behind.append(np.full(P, a[-1], np.int32))
+        elif nm.startswith("pv_"):
+            m = a.shape[0]
+            f, b = a[(np.arange(P) - P) % m].copy(), a[np.arange(P) % m].copy()
+            for x in (f, b):
+                if nm == "pv_bnum":
+                    x += 1
+                elif nm == "pv_handle":
+                    x += 7
+                elif nm == "pv_flags":
+                    x |= 1
+            front.append(f), behind.append(b)
+        elif nm == "acceptor":
+            front.append(a[(src_f + 1) % n].copy()), behind.append(a[(src_b + 1) % n].copy())
+        else:
+            front.append(a[src_f].copy()), behind.append(a[src_b].copy())
+    return front, behind
+
+
+def lay_out_wide(placement, columns):
+    """lay_out for columns of several lengths and widths: an 8-byte column takes its placement's offset rounded down to
+    a multiple of 8; under `packed` the 8-byte columns come first, then the 4-byte ones, then the bytes."""
+    chunks, pos = [], 0
+
+    def put(a):
+        nonlocal pos
+        chunks.append(a)
+        pos += a.shape[0]
+
+    def pad16(col):
+        if pos % 16:
+            k = 16 - pos % 16
+            put(np.full(k, SENTINEL, np.uint8) if col.out else np.zeros(k, np.uint8))
+    if placement == "packed":
+        for out in (False, True):
+            run = sorted([c for c in columns if c.out == out], key=lambda c: -c.width)
+            put(_band(run[0], GUARD, True))
+            for c in run:
+                c.off = pos
+                put(_body(c))
+            put(_band(run[-1], GUARD, False))
+            pad16(run[-1])
+    else:
+        for c in columns:
+            off = offsets_of(placement, c)
+            off -= off % c.width
+            assert pos % 16 == 0
+            put(_band(c, GUARD + off, True))
+            c.off = pos
+            assert c.off % 16 == off and c.off % c.width == 0
+            put(_body(c))
+            put(_band(c, GUARD, False))
+            pad16(c)
+    return np.concatenate(chunks)
+
+
+def elect_counts(log):
+    """{(entry point, placement): calls} of the view change's calls in a driver's log."""
+    out = {(op, p): 0 for op in ELECT_OPS for p in NAMES}
+    for x in log:
+        if x["op"] in ELECT_OPS:
+            out[(x["op"], x["placement"])] += 1
+    return out
+
+
+class ElectPlacer:
+    """Placer's two further entry points (mixed into the placed engines below): every input column and each of the
+    outputs - the four [window][n] planes among them - at its placement's offset inside one arena, between guard bands;
+    after the call the planes j >= e_count[i] of every record i are exactly the sentinel."""
+
+    def _placed_elect(self, op, arrays, W=1):
+        fn, ins, outs = ELECT_OPS[op]
+        n = int(arrays[0].shape[0])
+        k = self.count.get(op, 0)
+        placement = self.fixed or NAMES[k % len(NAMES)]
+        self.count[op] = k + 1
+        arrays = [np.ascontiguousarray(a, {1: np.uint8, 4: np.int32, 8: np.int64}[w]) for a, (_, w) in zip(arrays, ins)]
+        front, behind = elect_poison(op, arrays)
+        columns = [WideColumn(nm, w, a.shape[0], False, a, f, b) for (nm, w), a, f, b in zip(ins, arrays, front, behind)]
+        columns += [WideColumn(nm, w, n * W if nm in ELECT_PLANES else n, True) for nm, w in outs]
+        image = lay_out_wide(placement, columns)
+        what = f"{op} call {k + 1} of {n} records, placement {placement}"
+        after, kernels = self._run_elect(fn, n, image, columns)
+        verify(image, after, columns, what)
+        self.log.append(dict(op=op, n=n, placement=placement, kernels=kernels))
+        res = {c.name: after[c.off:c.off + c.nbytes].copy().view(c.dtype()) for c in columns if c.out}
+        if op == "prepare_reply":
+            cnt = res["e_count"].astype(np.int64)
+            assert (cnt >= 0).all() and (cnt <= W).all(), what
+            untouched = np.arange(W)[:, None] >= cnt[None, :]
+            for nm in ELECT_PLANES:
+                raw = after[[c for c in columns if c.name == nm][0].off:][:res[nm].nbytes].reshape(W, n, -1)
+                assert (raw[untouched] == SENTINEL).all(), f"{what}: {nm} written beyond e_count"
+        return n, res
+
+    def election_begin(self, gidx, bnum):
+        g = np.ascontiguousarray(gidx, np.int32)
+        _, r = self._placed_elect("election_begin", [g, np.array(np.broadcast_to(np.asarray(bnum, np.int32), g.shape))])
+        return r["e_status"]
+
+    def prepare_reply(self, gidx, acceptor, r_bnum, r_bcoord, first_slot, pvalues=None):
+        from tests.elect_enum_common import flatten, answer
+        g = np.ascontiguousarray(gidx, np.int32)
+        n = g.shape[0]
+        off, pv = flatten(pvalues if pvalues is not None else [[] for _ in range(n)])
+        assert off[-1] > 0, "the placed call wants at least one pvalue in the batch"
+        cols = [g] + [np.array(np.broadcast_to(np.asarray(x, np.int32), (n,))) for x in (acceptor, r_bnum, r_bcoord, first_slot)]
+        _, r = self._placed_elect("prepare_reply", cols + [off] + list(pv), int(self.e.cfg.window))
+        return answer(r, n)
+
+
+class PlacedDevEngine(Placer, ElectPlacer, DevEngine):
     """A HIP engine behind the host calls' signatures, every data-path call through gpx_*_batch_dev on columns placed in
     one device byte buffer.  The count word is read after gpx_compact_last_dev, like DevEngine's; `raw` is what the call
     itself left there.  prepare stays on the host call."""
@@ -311,6 +457,18 @@ class PlacedDevEngine(Placer, DevEngine):
     def __init__(self, e):
         DevEngine.__init__(self, e)
         self._init_placer()
+
+    def _run_elect(self, fn, n, image, columns):
+        buf = self.t.from_numpy(image).cuda()
+        base = buf.data_ptr()
+        assert base % 16 == 0
+        args = [C.c_void_p(base + c.off) for c in columns]
+        if fn == "prepare_reply_batch":
+            args.insert(6, int(columns[6].n))   # pv_total, behind pv_off: the entries of the pvalue columns
+        self._begin()
+        self.e.lib.check(self.e.lib.fn[fn + "_dev"](self.e.h, n, *args), fn + "_dev")
+        self._finish(None)
+        return buf.cpu().numpy(), self.kernels[-1]
 
     def _run(self, fn, n, image, columns):
         buf = self.t.from_numpy(image).cuda()
@@ -323,12 +481,19 @@ class PlacedDevEngine(Placer, DevEngine):
         return buf.cpu().numpy(), self.kernels[-1]
 
 
-class PlacedHostEngine(Placer):
+class PlacedHostEngine(Placer, ElectPlacer):
     """The same arenas over numpy bytes: a library's host-pointer calls (the oracle's) on placed columns."""
 
     def __init__(self, e):
         self.e, self.raw = e, None
         self._init_placer()
+
+    def _run_elect(self, fn, n, image, columns):
+        arena = aligned_bytes(image.shape[0])
+        arena[:] = image
+        args = [C.c_void_p(arena.ctypes.data + c.off) for c in columns]
+        self.e.lib.check(self.e.lib.fn[fn](self.e.h, n, *args), fn)
+        return arena, set()
 
     def __getattr__(self, name):
         return getattr(self.e, name)

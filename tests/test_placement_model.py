@@ -129,6 +129,74 @@ def test_every_pair_three_times_over_the_file():
     assert len(CELLS) >= 3 and set(PC.PLACED_STEPS) == set(CELLS)
 
 
+@pytest.mark.parametrize("W", [8, 64])
+def test_view_change_entry_points_under_every_placement(oracle_lib, W):
+    """gpx_election_begin and gpx_prepare_reply_batch: test_elect_enum_gpu.py's placed legs over numpy bytes through the
+    oracle's host pointers - every (entry point, placement) pair occurs, guards and planes checked as on the GPU."""
+    from tests import elect_enum_common as EC
+    from tests.test_elect_enum_gpu import PLACED_SAMPLE
+    counts = {}
+    for placement in PC.NAMES:
+        def placed(e):
+            p = PC.PlacedHostEngine(e)
+            p.fixed = placement
+            return p
+        st = EC.run_enum(oracle_lib, 3, W, 3, "wrap" if W == 64 else "plain", "dev", sample=PLACED_SAMPLE, driver=placed)
+        for k, v in PC.elect_counts(st.driver.log).items():
+            counts[k] = counts.get(k, 0) + v
+    assert set(counts) == {(op, p) for op in PC.ELECT_ENTRY_POINTS for p in PC.NAMES} and all(v >= 1 for v in counts.values()), counts
+
+
+def test_view_change_planes_and_wide_columns():
+    """lay_out_wide: 8-byte columns on 8-byte boundaries under every placement, every column between its guards."""
+    n, W, m = 5, 8, 7
+    for placement in PC.NAMES:
+        cols = [PC.WideColumn("gidx", 4, n, False, np.arange(n, dtype=np.int32), np.zeros(PC.P, np.int32), np.ones(PC.P, np.int32)),
+                PC.WideColumn("pv_handle", 8, m, False, np.arange(m, dtype=np.int64), np.zeros(PC.P, np.int64), np.ones(PC.P, np.int64)),
+                PC.WideColumn("pv_flags", 1, m, False, np.zeros(m, np.uint8), np.zeros(PC.P, np.uint8), np.ones(PC.P, np.uint8)),
+                PC.WideColumn("e_handle", 8, n * W, True), PC.WideColumn("e_slot", 4, n * W, True), PC.WideColumn("status", 1, n, True)]
+        img = PC.lay_out_wide(placement, cols)
+        spans = sorted((c.off, c.off + c.nbytes, c) for c in cols)
+        assert spans[0][0] >= PC.GUARD and img.shape[0] - spans[-1][1] >= PC.GUARD
+        for (a0, a1, a), (b0, b1, b) in zip(spans, spans[1:]):
+            assert b0 - a1 >= 2 * PC.GUARD or (placement == "packed" and b0 == a1 and a.out == b.out), (placement, a.name, b.name)
+        for c in cols:
+            assert c.off % c.width == 0
+            if c.out:
+                assert (img[c.off:c.off + c.nbytes] == PC.SENTINEL).all()
+            else:
+                assert img[c.off:c.off + c.nbytes].tobytes() == c.body.tobytes()
+
+
+def test_view_change_poison_is_live(oracle_lib):
+    """Handed to the oracle as records, the band behind the record columns changes the state of the group of record
+    n - 1; one entry of the band behind the pvalue columns, read by the last record, changes what that group carries."""
+    from tests import elect_enum_common as EC
+    S0 = EC.BASES["plain"]
+    g = np.arange(4, dtype=np.int32)
+    acc = np.array([101, 7, 5000, 7], np.int32)
+    pvalues = [[(S0, 0, 7, 600 + i, 0)] for i in range(4)]
+    off, pv = EC.flatten(pvalues)
+    cols = [g, acc, np.full(4, EC.BNUM, np.int32), np.full(4, EC.ME, np.int32), np.full(4, S0, np.int32)]
+    front, behind = PC.elect_poison("prepare_reply", cols + [off] + list(pv))
+
+    def dumps(cols_, pvalues_):
+        e = EC.make_engine(oracle_lib, 3, 8, 4, S0, 64)
+        assert (e.election_begin(g, np.full(4, EC.BNUM, np.int32)) == 0).all()
+        e.prepare_reply(*cols_, pvalues_)
+        out = [e.dump(int(x)).tolist() for x in g]
+        e.close()
+        return out
+    plain = dumps(cols, pvalues)
+    ext = [np.concatenate([c, b]) for c, b in zip(cols, behind[:5])]
+    assert dumps(ext, pvalues + [[] for _ in range(PC.P)])[3] != plain[3]
+    extra = tuple(int(behind[6 + i][0]) for i in range(5))
+    assert extra[1] == 1 and extra[4] & 1 and extra[3] != 600
+    assert dumps(cols, pvalues[:3] + [pvalues[3] + [extra]])[3] != plain[3]
+    pre = [np.concatenate([f, c]) for c, f in zip(cols, front[:5])]
+    assert dumps(pre, [[] for _ in range(PC.P)] + pvalues)[0] != plain[0]
+
+
 @pytest.mark.parametrize("kind,n", MODEL_CASES)
 def test_directed_cases_with_live_poison(oracle_lib, kind, n):
     """Every case of test_placement_gpu.py's tails, the oracle through placed numpy columns against the oracle; then

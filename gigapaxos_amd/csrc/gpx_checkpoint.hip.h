@@ -1,36 +1,26 @@
 // Checkpoint transfer (include/gpx_checkpoint.h): PISM.handleCheckpoint's acceptor half - PaxosAcceptor.jumpSlot, then
 // extractExecuteAndCheckpoint(null) - for one record per group, the execution runs compacted in record order.
 //
-// A call is three launches on one stream, the scheme of gpx_scan.hip.h / gpx_sweep.hip.h; no workgroup ever waits for
-// another one:
+// The three launches, the scratch invariant and the bounds argument: gpx_compact.hip.h.  What is this call's own:
 //
-//   k_cp_tile<PEEK>  one workgroup per GPX_CP_TILE consecutive records, one lane per record.  The lane asks for its
-//                    record, then for the group's words, then for the ring entries it will need - the ones the jump
-//                    walks (fewer than W, or all W of them) and the one at the slot the tail starts from - in rounds of
-//                    GPX_CP_ROUND independent 16-byte loads; applies steps 1-4 of the header and stores the dense
-//                    outputs.  A run parks (group, first, count) at the tile's base + its rank (the wave's ballot below
-//                    the lane + the per-wave prefix in LDS).  The tile's four counts go to tile[t], unconditionally.
-//                    UNLIKE THE SWEEP, STATE CHANGES HERE: no cap decides which records are applied, so nothing has to
-//                    wait for the offsets.  PEEK = true loads no ring entry and stores no state.
-//   k_cp_offsets     ONE workgroup: the exclusive prefix of the tiles' run counts replaces tile[t].x (the adopted count,
-//                    summed by then), the four sums go to *counts.
-//   k_cp_move        one workgroup per tile: parked run j of tile t is output entry tile[t].x + j.  Not launched under
-//                    PEEK (no runs).
+//   k_cp_tile<PEEK>  GPX_CP_TILE records, one lane per record.  The lane asks for its record, then for the group's words,
+//                    then for the ring entries it will need - the ones the jump walks (fewer than W, or all W of them) and
+//                    the one at the slot the tail starts from - in rounds of GPX_CP_ROUND independent 16-byte loads;
+//                    applies steps 1-4 of the header and stores the dense outputs.  A run parks (group, first, count).
+//                    The tile's four counts go to tile[t], one 16-byte word.  UNLIKE THE SWEEP, STATE CHANGES HERE: no
+//                    cap decides which records are applied, so nothing has to wait for the offsets.  PEEK = true loads no
+//                    ring entry and stores no state.
+//   k_cp_offsets     the exclusive prefix of the tiles' run counts replaces tile[t].x (the adopted count, summed by
+//                    then), the four sums go to *counts.
+//   k_cp_move        parked run j of tile t is output entry tile[t].x + j: no cap, every run column holds n entries and
+//                    n_runs <= n.  Not launched under PEEK (no runs).
 //
-// SCRATCH INVARIANT, as in gpx_scan.hip.h: every scratch word a call reads is one the SAME call wrote.  k_cp_offsets
-// reads tile[0, ntiles): each written whole by its tile's workgroup.  k_cp_move reads tile[t].x (k_cp_offsets, every
-// t < ntiles), tile[t].w and parked entries j < tile[t].w of tile t: exactly what that tile's workgroup wrote.
-//
-// Bounds: a parked entry sits at tile * GPX_CP_TILE + rank with rank < GPX_CP_TILE; the parked columns hold
-// max(max_groups, max_batch) entries rounded up to whole tiles and the host refuses a larger n.  A group number indexes
-// state only after it has been checked against S.G; a ring index is masked with W - 1.  An output index is below
-// n_runs <= n, and every run column holds n entries.
+// A ring index is masked with W - 1.
 //
 // Distinct groups (a precondition, as for gpx_election_begin_dev): two records naming one group would race on its state.
 #pragma once
 
 #define GPX_CP_TILE 256 /* == GPX_BLOCK: one lane per record */
-#define GPX_CP_WAVES (GPX_CP_TILE / 64)
 #define GPX_CP_ROUND 4 /* ring entries requested together */
 #define GPX_CP_PEEK_ 1 /* == GPX_CP_PEEK / _ADOPT / _MOVED of include/gpx_checkpoint.h (checked in gpx_checkpoint_dev.inc) */
 #define GPX_CP_ADOPT_ 1
@@ -45,11 +35,6 @@ struct CpMem {
   int32_t *park_g, *park_first, *park_count; /* [whole tiles] */
   I4* tile; /* [tiles] {adopted, no group, stopped, runs}; .x becomes the tile's first output entry (k_cp_offsets) */
 };
-
-/* lanes of this wave below the caller's whose bit is set in m */
-__device__ __forceinline__ int32_t cp_rank_below(unsigned long long m) {
-  return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 /* PaxosAcceptor.jumpSlot(target) (PaxosAcceptor.java:564-578) for d = target - slot > 0: committedRequests.remove(i)
  * and, from disk, acceptedProposals.remove(i) for every i of [slot, target); executed(i, false) only counts.  A key k
@@ -143,9 +128,8 @@ __global__ __launch_bounds__(GPX_CP_TILE) void k_cp_tile(DevState S, int32_t n, 
                                                         int32_t* __restrict__ o_from, int32_t* __restrict__ o_to,
                                                         uint8_t* __restrict__ o_flags, uint8_t* __restrict__ status,
                                                         CpMem M) {
-  __shared__ int32_t w_cnt[4][GPX_CP_WAVES];
+  __shared__ int32_t w_cnt[4][GPX_COMPACT_WAVES];
   const int32_t t0 = (int32_t)blockIdx.x * GPX_CP_TILE; /* n <= 2^31 - 1: the last tile's base fits */
-  const int32_t wave = (int32_t)threadIdx.x >> 6;
   const int64_t i = (int64_t)t0 + (int32_t)threadIdx.x;
   bool adopt = false, ng = false, st = false;
   int32_t g = 0, first = 0, count = 0;
@@ -192,77 +176,27 @@ __global__ __launch_bounds__(GPX_CP_TILE) void k_cp_tile(DevState S, int32_t n, 
     status[i] = (uint8_t)(ng ? GPX_S_NOGROUP : st ? GPX_S_STOPPED : GPX_S_OK);
   }
   const bool run = count > 0;
-  const unsigned long long ma = __ballot(adopt), mn = __ballot(ng), ms = __ballot(st), mr = __ballot(run);
-  if ((threadIdx.x & 63) == 0) {
-    w_cnt[0][wave] = __popcll(ma);
-    w_cnt[1][wave] = __popcll(mn);
-    w_cnt[2][wave] = __popcll(ms);
-    w_cnt[3][wave] = __popcll(mr);
-  }
-  __syncthreads();
-  int32_t before = 0, na = 0, nn = 0, ns = 0, nr = 0;
-#pragma unroll
-  for (int32_t q = 0; q < GPX_CP_WAVES; q++) {
-    const int32_t c = w_cnt[3][q];
-    before += q < wave ? c : 0;
-    na += w_cnt[0][q];
-    nn += w_cnt[1][q];
-    ns += w_cnt[2][q];
-    nr += c;
-  }
+  const TileCount<4> c = tile_count(w_cnt, {adopt, ng, st, run});
   if (run) {
-    const int32_t p = t0 + before + cp_rank_below(mr);
+    const int32_t p = t0 + c.before[3];
     M.park_g[p] = g;
     M.park_first[p] = first;
     M.park_count[p] = count;
   }
-  if (threadIdx.x == 0) M.tile[blockIdx.x] = mk4(na, nn, ns, nr);
+  if (threadIdx.x == 0) M.tile[blockIdx.x] = mk4(c.total[0], c.total[1], c.total[2], c.total[3]);
 }
 
-/* one workgroup: tile[t].x = exclusive prefix of the tiles' run counts, *counts = the four sums (k_scan_offsets' body
- * over four words) */
+/* one workgroup: tile[t].x = exclusive prefix of the tiles' run counts, *counts = the four sums */
 __global__ __launch_bounds__(GPX_CP_TILE) void k_cp_offsets(int32_t ntiles, CpMem M, CpCounts* __restrict__ counts) {
-  __shared__ int32_t w_sum[4][GPX_CP_WAVES];
-  const int32_t lane = (int32_t)threadIdx.x & 63, wave = (int32_t)threadIdx.x >> 6;
-  int32_t running = 0, adp = 0, nog = 0, stp = 0;
-  for (int32_t t0 = 0; t0 < ntiles; t0 += GPX_CP_TILE) {
-    const int32_t t = t0 + (int32_t)threadIdx.x;
-    const I4 v = t < ntiles ? M.tile[t] : mk4(0, 0, 0, 0);
-    const int32_t c = v.w;
-    int32_t ad = v.x, ng = v.y, sp = v.z;
-    int32_t inc = c; /* inclusive prefix within the wave */
-#pragma unroll
-    for (int32_t d = 1; d < 64; d <<= 1) {
-      const int32_t u = __shfl_up(inc, d);
-      const int32_t x = __shfl_xor(ad, d);
-      const int32_t y = __shfl_xor(ng, d);
-      const int32_t z = __shfl_xor(sp, d);
-      if (lane >= d) inc += u;
-      ad += x; /* butterflies: every lane ends with the wave's sum */
-      ng += y;
-      sp += z;
-    }
-    if (lane == 63) {
-      w_sum[0][wave] = inc;
-      w_sum[1][wave] = ad;
-      w_sum[2][wave] = ng;
-      w_sum[3][wave] = sp;
-    }
-    __syncthreads();
-    int32_t before = 0, total = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_CP_WAVES; q++) {
-      before += q < wave ? w_sum[0][q] : 0;
-      total += w_sum[0][q];
-      adp += w_sum[1][q];
-      nog += w_sum[2][q];
-      stp += w_sum[3][q];
-    }
-    if (t < ntiles) M.tile[t].x = running + before + inc - c;
-    running += total;
-    __syncthreads(); /* w_sum is rewritten by the next round */
-  }
-  if (threadIdx.x == 0) *counts = CpCounts{adp, nog, stp, running};
+  int32_t sum[4];
+  tile_offsets<1, 3>(
+      ntiles,
+      [&](int32_t t, int32_t(&v)[4]) {
+        const I4 w = M.tile[t];
+        v[0] = w.w, v[1] = w.x, v[2] = w.y, v[3] = w.z;
+      },
+      [&](int32_t t, const int32_t(&off)[1], const int32_t(&)[4]) { M.tile[t].x = off[0]; }, sum);
+  if (threadIdx.x == 0) *counts = CpCounts{sum[1], sum[2], sum[3], sum[0]};
 }
 
 __global__ __launch_bounds__(GPX_CP_TILE) void k_cp_move(CpMem M, int32_t* __restrict__ x_gidx,

@@ -1,6 +1,6 @@
 // Device-pointer side of the checkpoint transfer (include/gpx_checkpoint.h; kernels in gpx_checkpoint.hip.h): the
 // scratch, the checks and gpx_checkpoint_batch_dev; the host-pointer twin: gpx_checkpoint_host.inc.
-// Needs: the engine and the kernels of gpx_engine.hip, scan_max_n / scan_init (gpx_scan_dev.inc).
+// Needs: the engine and the kernels of gpx_engine.hip, scan_init (gpx_scan_dev.inc), gpx_ctl_block.inc.
 
 namespace {
 
@@ -20,40 +20,22 @@ int cp_args(const gpx_engine* h, int32_t n, const void* gidx, const void* cp_slo
 }
 
 /* The parked runs (12 bytes per record of max(max_groups, max_batch) in whole tiles), the per-tile words (16 bytes) and
- * the host twin's counts.  They lie in the scan family's block where that is large enough - the calls share a stream,
- * and a call reads only what it wrote itself - else in a block of their own, allocated by the first call.  Not cleared.
- * A failed allocation leaves nothing behind and the engine usable. */
+ * the host twin's counts.  They lie in the scan family's block where that is large enough, else in a block of their
+ * own, allocated by the first call (ctl_block).  Not cleared. */
 int cp_init(gpx_engine* e) {
   if (e->cp_counts) return GPX_OK;
-  const size_t tiles = std::max<size_t>(((size_t)scan_max_n(e) + GPX_CP_TILE - 1) / GPX_CP_TILE, 1);
-  const size_t cap = tiles * GPX_CP_TILE;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_col = up(cap * 4), b_tl = up(tiles * sizeof(I4));
-  const size_t need = 3 * b_col + b_tl + 256;
+  const size_t tiles = ctl_tiles(e, GPX_CP_TILE), cap = tiles * GPX_CP_TILE;
   int rc = scan_init(e);
   if (rc != GPX_OK) return rc;
-  char* base = e->scan.base;
-  if ((size_t)26 * e->scan.cap + (size_t)3 * e->scan.tl < need) {
-    base = nullptr;
-    if ((rc = dev_alloc(e, &base, need, false)) != GPX_OK) return rc;
-  }
   CpMem& M = e->cp;
-  char* p = base;
-  M.park_g = (int32_t*)p, p += b_col;
-  M.park_first = (int32_t*)p, p += b_col;
-  M.park_count = (int32_t*)p, p += b_col;
-  M.tile = (I4*)p, p += b_tl;
-  e->cp_counts = (CpCounts*)p; /* last: the marker */
-  return GPX_OK;
+  return ctl_block(e,
+                   {ctl_col(&M.park_g, cap), ctl_col(&M.park_first, cap), ctl_col(&M.park_count, cap),
+                    ctl_col(&M.tile, tiles), ctl_col(&e->cp_counts, 1)},
+                   false, e->scan.base, (size_t)26 * e->scan.cap + (size_t)3 * e->scan.tl);
 }
 
-/* what the call needs of the engine: the size limit, an engine an exchange kernel gave up on, the scratch */
-int cp_open(gpx_engine* h, int32_t n) {
-  if ((int64_t)n > scan_max_n(h)) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  return cp_init(h);
-}
+/* ctl_open for this family, under the name its host-pointer twin calls */
+int cp_open(gpx_engine* h, int32_t n) { return ctl_open(h, n, scan_max_n(h), cp_init); }
 
 }  // namespace
 
@@ -67,7 +49,7 @@ int gpx_checkpoint_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, cons
   if ((rc = cp_open(h, n)) != GPX_OK) return rc;
   h->stream = h->sB;
   const bool peek = (flags & GPX_CP_PEEK) != 0;
-  const int ntiles = (int)(((int64_t)n + GPX_CP_TILE - 1) / GPX_CP_TILE);
+  const int ntiles = tiles_for(n, GPX_CP_TILE);
   if (ntiles && peek)
     LAUNCH(h, "k_cp_tile_peek", (k_cp_tile<true>), ntiles, h->S, n, gidx, cp_slot, o_from, o_to, o_flags, status, h->cp);
   if (ntiles && !peek)

@@ -20,10 +20,9 @@
 //                    also retires the group, after it has read the last word of it.
 // APPLY is the import's two launches with the replace rule (image_rows_body<., true>) and k_delta_gone.
 //
-// SCRATCH INVARIANT, as in gpx_image.hip.h: a call reads only scratch words it wrote itself.  k_delta_offsets reads the
-// four per-tile words of tiles [0, ntiles) and parked entries below tile_chg of the cut tile; k_delta_move reads
-// tile_chg / tile_off / tile_gone / tile_xoff of its tile and parked entries below tile_chg / tile_gone.  The marks are
-// not scratch: engine state, zeroed when allocated, touched by k_delta_tile (read) and k_delta_move (write) alone.
+// SCRATCH INVARIANT (gpx_compact.hip.h): beyond the per-tile words k_delta_offsets reads parked entries below tile_chg of
+// the cut tile; k_delta_move reads parked entries below tile_chg / tile_gone of its tile.  The marks are not scratch:
+// engine state, zeroed when allocated, touched by k_delta_tile (read) and k_delta_move (write) alone.
 //
 // Bounds.  A parked entry sits at tile * GPX_IMAGE_TILE + rank, rank < GPX_IMAGE_TILE; the host refuses n above the
 // entries the parked columns hold.  A group number indexes state or marks only after it has been compared with S.G
@@ -168,9 +167,8 @@ __device__ __forceinline__ unsigned long long delta_sig(const DevState& S, int32
 
 __global__ __launch_bounds__(GPX_BLOCK) void k_delta_tile(DevState S, int32_t n, const int32_t* __restrict__ gidx,
                                                          int32_t g_base, int32_t flags, DeltaMem M) {
-  __shared__ int32_t w_cnt[4][GPX_IMAGE_WAVES];
+  __shared__ int32_t w_cnt[4][GPX_COMPACT_WAVES];
   const int32_t t0 = (int32_t)blockIdx.x * GPX_IMAGE_TILE;
-  const int32_t wave = (int32_t)threadIdx.x >> 6;
   const int64_t i = (int64_t)t0 + (int32_t)threadIdx.x;
   bool live = false, prep = false, chg = false, gone = false;
   int32_t g = 0;
@@ -191,101 +189,47 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_delta_tile(DevState S, int32_t n,
       }
     }
   }
-  const unsigned long long ml = __ballot(live), mc = __ballot(chg), mp = __ballot(chg && prep), mg = __ballot(gone);
-  if ((threadIdx.x & 63) == 0) {
-    w_cnt[0][wave] = __popcll(ml);
-    w_cnt[1][wave] = __popcll(mc);
-    w_cnt[2][wave] = __popcll(mp);
-    w_cnt[3][wave] = __popcll(mg);
-  }
-  __syncthreads();
-  int32_t before_c = 0, before_g = 0, tl = 0, tc = 0, tp = 0, tg = 0;
-#pragma unroll
-  for (int32_t q = 0; q < GPX_IMAGE_WAVES; q++) {
-    before_c += q < wave ? w_cnt[1][q] : 0;
-    before_g += q < wave ? w_cnt[3][q] : 0;
-    tl += w_cnt[0][q];
-    tc += w_cnt[1][q];
-    tp += w_cnt[2][q];
-    tg += w_cnt[3][q];
-  }
+  const TileCount<4> c = tile_count(w_cnt, {live, chg, chg && prep, gone});
   if (chg) {
-    const int32_t p = t0 + before_c + sweep_rank_below(mc);
+    const int32_t p = t0 + c.before[1];
     M.park[p] = (int32_t)((uint32_t)g | (prep ? GPX_IMAGE_PREP : 0u));
     M.park_sig[p] = sig;
   }
-  if (gone) M.park_gone[t0 + before_g + sweep_rank_below(mg)] = g;
+  if (gone) M.park_gone[t0 + c.before[3]] = g;
   if (threadIdx.x == 0) {
-    M.tile_live[blockIdx.x] = tl;
-    M.tile_chg[blockIdx.x] = tc;
-    M.tile_rows[blockIdx.x] = tc + tp;
-    M.tile_gone[blockIdx.x] = tg;
+    M.tile_live[blockIdx.x] = c.total[0];
+    M.tile_chg[blockIdx.x] = c.total[1];
+    M.tile_rows[blockIdx.x] = c.total[1] + c.total[2];
+    M.tile_gone[blockIdx.x] = c.total[3];
   }
 }
 
 __global__ __launch_bounds__(GPX_BLOCK) void k_delta_offsets(int32_t ntiles, DeltaMem M, int32_t cap, int32_t cap_gone,
                                                             DeltaCounts* __restrict__ counts) {
-  __shared__ int32_t w_sum[4][GPX_IMAGE_WAVES];
   __shared__ int32_t s_cut;
-  const int32_t lane = (int32_t)threadIdx.x & 63, wave = (int32_t)threadIdx.x >> 6;
   if (threadIdx.x == 0) s_cut = -1;
-  int32_t run_r = 0, run_c = 0, run_x = 0, run_l = 0;
-  for (int32_t tb = 0; tb < ntiles; tb += GPX_BLOCK) {
-    const int32_t t = tb + (int32_t)threadIdx.x;
-    const int32_t r = t < ntiles ? M.tile_rows[t] : 0;
-    const int32_t c = t < ntiles ? M.tile_chg[t] : 0;
-    const int32_t x = t < ntiles ? M.tile_gone[t] : 0;
-    const int32_t l = t < ntiles ? M.tile_live[t] : 0;
-    const int32_t ir = wave_incscan(r), ic = wave_incscan(c), ix = wave_incscan(x), il = wave_incscan(l);
-    __syncthreads(); /* w_sum of the round before has been read; s_cut is initialised */
-    if (lane == 63) {
-      w_sum[0][wave] = ir;
-      w_sum[1][wave] = ic;
-      w_sum[2][wave] = ix;
-      w_sum[3][wave] = il;
-    }
-    __syncthreads();
-    int32_t br = 0, bc = 0, bx = 0, tr = 0, tc = 0, tx = 0, tl = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_IMAGE_WAVES; q++) {
-      br += q < wave ? w_sum[0][q] : 0;
-      bc += q < wave ? w_sum[1][q] : 0;
-      bx += q < wave ? w_sum[2][q] : 0;
-      tr += w_sum[0][q];
-      tc += w_sum[1][q];
-      tx += w_sum[2][q];
-      tl += w_sum[3][q];
-    }
-    if (t < ntiles) {
-      const int32_t off = run_r + br + ir - r;
-      M.tile_off[t] = off;
-      M.tile_goff[t] = run_c + bc + ic - c;
-      M.tile_xoff[t] = run_x + bx + ix - x;
-      if (off <= cap && (int64_t)off + r > cap) s_cut = t; /* at most one tile: offsets ascend */
-    }
-    run_r += tr;
-    run_c += tc;
-    run_x += tx;
-    run_l += tl;
-  }
-  __syncthreads();
+  int32_t sum[4]; /* rows, changed, gone, live */
+  tile_offsets<3, 1>(
+      ntiles,
+      [&](int32_t t, int32_t(&v)[4]) { v[0] = M.tile_rows[t], v[1] = M.tile_chg[t], v[2] = M.tile_gone[t], v[3] = M.tile_live[t]; },
+      [&](int32_t t, const int32_t(&off)[3], const int32_t(&v)[4]) {
+        M.tile_off[t] = off[0];
+        M.tile_goff[t] = off[1];
+        M.tile_xoff[t] = off[2];
+        if (off[0] <= cap && (int64_t)off[0] + v[0] > cap) s_cut = t; /* at most one tile: offsets ascend */
+      },
+      sum);
+  __syncthreads(); /* s_cut: initialised (ntiles == 0: no barrier above) or stored */
   const int32_t cut = s_cut; /* the same in every lane */
-  int32_t n_done = run_c, n_rows_done = run_r;
+  int32_t n_done = sum[1], n_rows_done = sum[0];
   if (cut >= 0) {
-    /* the tile `cap` cuts: the entries of it that still fit (its own words: written above, by this workgroup).  They
-     * are a prefix of the tile's entries, so the block's totals of (fits, rows of the ones that fit) are the answer. */
+    /* the tile `cap` cuts: the entries of it that still fit (its own words: written above, by this workgroup) */
     const int32_t c = M.tile_chg[cut], off = M.tile_off[cut], j = (int32_t)threadIdx.x;
-    const int32_t e = j < c ? M.park[(int64_t)cut * GPX_IMAGE_TILE + j] : 0;
-    const int32_t w = j < c ? (e < 0 ? 2 : 1) : 0;
-    int32_t tot = 0, nd = 0, nr = 0;
-    const int32_t pre = block_exscan(w, &tot);
-    const bool fits = j < c && (int64_t)off + pre + w <= cap;
-    block_exscan(fits ? 1 : 0, &nd);
-    block_exscan(fits ? w : 0, &nr);
-    n_done = M.tile_goff[cut] + nd;
-    n_rows_done = off + nr;
+    const CapCut f = cap_cut(off, j < c ? image_weight(M.park[(int64_t)cut * GPX_IMAGE_TILE + j]) : 0, cap);
+    n_done = M.tile_goff[cut] + f.n;
+    n_rows_done = off + f.rows;
   }
-  if (threadIdx.x == 0) *counts = DeltaCounts{run_l, run_c, run_r, n_done, n_rows_done, run_x, min(run_x, cap_gone), 0};
+  if (threadIdx.x == 0) *counts = DeltaCounts{sum[3], sum[1], sum[0], n_done, n_rows_done, sum[2], min(sum[2], cap_gone), 0};
 }
 
 __global__ __launch_bounds__(GPX_BLOCK) void k_delta_move(DevState S, DeltaMem M, NameCopies names, ImageIdle idle,
@@ -295,11 +239,11 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_delta_move(DevState S, DeltaMem M
   __shared__ int32_t s_main[GPX_IMAGE_TILE], s_cont[GPX_IMAGE_TILE];
   const int32_t j = (int32_t)threadIdx.x;
   const int64_t p0 = (int64_t)blockIdx.x * GPX_IMAGE_TILE;
-  { /* the gone entries below cap_gone (xoff <= n_gone <= 2^31 - 1, cap_gone >= 0: no overflow) */
-    const int32_t cx = M.tile_gone[blockIdx.x], xoff = M.tile_xoff[blockIdx.x];
-    if (j < min(cx, cap_gone - xoff)) {
+  { /* the gone entries below cap_gone */
+    const MoveSpan x = move_span<GPX_IMAGE_TILE>(M.tile_gone, M.tile_xoff, cap_gone);
+    if (j < x.lim) {
       const int32_t g = M.park_gone[p0 + j];
-      o_gone[xoff + j] = g;
+      o_gone[x.off + j] = g;
       M.marks[g] = 0ull;
     }
   }
@@ -308,10 +252,8 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_delta_move(DevState S, DeltaMem M
   const int32_t e = j < c ? M.park[p0 + j] : 0;
   const int32_t g = (int32_t)((uint32_t)e & ~GPX_IMAGE_PREP);
   const bool prep = e < 0;
-  const int32_t w = j < c ? (prep ? 2 : 1) : 0;
-  int32_t tot = 0;
-  const int32_t pre = block_exscan(w, &tot);
-  const bool fits = j < c && (int64_t)off + pre + w <= cap;
+  int32_t pre = 0;
+  const bool fits = weighted_fits(off, j < c ? image_weight(e) : 0, cap, &pre);
   s_main[j] = fits ? off + pre : -1;
   s_cont[j] = fits && prep ? off + pre + 1 : -1;
   const int any_cont = __syncthreads_or(fits && prep);

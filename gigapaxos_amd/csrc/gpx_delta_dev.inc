@@ -1,6 +1,6 @@
 // Device-pointer side of the delta images (include/gpx_delta.h; kernels in gpx_delta.hip.h): the argument checks, the
 // marks and the scratch, and the two *_dev calls; the host-pointer twins: gpx_delta_host.inc.
-// Needs: gpx_image_dev.inc (image_open, image_import_open, image_names, image_idle), scan_max_n (gpx_scan_dev.inc).
+// Needs: gpx_image_dev.inc (image_open, image_import_open, image_names, image_idle), gpx_ctl_block.inc.
 
 namespace {
 
@@ -24,34 +24,19 @@ int delta_apply_args(const gpx_engine* h, int32_t n_rows, const void* rows, int3
   return GPX_OK;
 }
 
-/* The marks over max_groups, the parked entries, the per-tile words and the host twins' counts: ONE block, allocated by
- * the first delta export.  Zeroed: a mark starts at "never written" (the rest is scratch, of which a call reads only
- * what it wrote).  A failed allocation leaves nothing behind and the engine usable. */
+/* The marks over max_groups, the parked entries, the per-tile words and the host twins' counts: ONE block (ctl_block),
+ * allocated by the first delta export.  Zeroed: a mark starts at "never written". */
 int delta_init(gpx_engine* e) {
   if (e->delta_counts) return GPX_OK;
   const size_t G = (size_t)std::max(e->cfg.max_groups, 1);
-  const size_t tiles = std::max<size_t>(((size_t)scan_max_n(e) + GPX_IMAGE_TILE - 1) / GPX_IMAGE_TILE, 1);
-  const size_t cap = tiles * GPX_IMAGE_TILE;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_mk = up(G * 8), b_ps = up(cap * 8), b_pk = up(cap * 4), b_tl = up(tiles * 4);
-  char* base = nullptr;
-  int rc = dev_alloc(e, &base, b_mk + b_ps + 2 * b_pk + 7 * b_tl + 256, true);
-  if (rc != GPX_OK) return rc;
+  const size_t tiles = ctl_tiles(e, GPX_IMAGE_TILE), cap = tiles * GPX_IMAGE_TILE;
   DeltaMem& M = e->delta;
-  char* p = base;
-  M.marks = (unsigned long long*)p, p += b_mk;
-  M.park_sig = (unsigned long long*)p, p += b_ps;
-  M.park = (int32_t*)p, p += b_pk;
-  M.park_gone = (int32_t*)p, p += b_pk;
-  M.tile_live = (int32_t*)p, p += b_tl;
-  M.tile_chg = (int32_t*)p, p += b_tl;
-  M.tile_rows = (int32_t*)p, p += b_tl;
-  M.tile_gone = (int32_t*)p, p += b_tl;
-  M.tile_off = (int32_t*)p, p += b_tl;
-  M.tile_goff = (int32_t*)p, p += b_tl;
-  M.tile_xoff = (int32_t*)p, p += b_tl;
-  e->delta_counts = (DeltaCounts*)p; /* last: the marker */
-  return GPX_OK;
+  return ctl_block(e,
+                   {ctl_col(&M.marks, G), ctl_col(&M.park_sig, cap), ctl_col(&M.park, cap), ctl_col(&M.park_gone, cap),
+                    ctl_col(&M.tile_live, tiles), ctl_col(&M.tile_chg, tiles), ctl_col(&M.tile_rows, tiles),
+                    ctl_col(&M.tile_gone, tiles), ctl_col(&M.tile_off, tiles), ctl_col(&M.tile_goff, tiles),
+                    ctl_col(&M.tile_xoff, tiles), ctl_col(&e->delta_counts, 1)},
+                   true);
 }
 
 int delta_export_open(gpx_engine* h, int32_t n) {
@@ -64,7 +49,7 @@ int delta_export_open(gpx_engine* h, int32_t n) {
 int delta_export_run(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t g_base, int32_t flags, int32_t cap,
                      void* o_rows, int32_t cap_gone, int32_t* o_gone, gpx_delta_counts* counts) {
   h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n + GPX_IMAGE_TILE - 1) / GPX_IMAGE_TILE);
+  const int ntiles = tiles_for(n, GPX_IMAGE_TILE);
   if (ntiles) LAUNCH(h, "k_delta_tile", k_delta_tile, ntiles, h->S, n, gidx, g_base, flags, h->delta);
   LAUNCH(h, "k_delta_offsets", k_delta_offsets, 1, (int32_t)ntiles, h->delta, cap, cap_gone, (DeltaCounts*)counts);
   if (ntiles && (cap > 0 || cap_gone > 0))
@@ -77,7 +62,7 @@ int delta_export_run(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t g_ba
 /* the import's two launches with the replace rule */
 int delta_rows_run(gpx_engine* h, int32_t n_rows, const void* rows, const int32_t* gidx, uint8_t* status) {
   h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n_rows + GPX_IMAGE_TILE - 1) / GPX_IMAGE_TILE);
+  const int ntiles = tiles_for(n_rows, GPX_IMAGE_TILE);
   if (!ntiles) return GPX_OK;
   LAUNCH(h, "k_delta_check", k_delta_rows<false>, ntiles, h->S, h->img, image_names(h), image_idle(h), n_rows,
          (const int32_t*)rows, gidx, status);

@@ -38,6 +38,7 @@
 #include "gpx_elect.hip.h"
 #include "gpx_packed.hip.h"
 #include "gpx_packed_out.hip.h"
+#include "gpx_compact.hip.h"
 #include "../../include/gpx_scan.h"
 #include "gpx_scan.hip.h"
 #include "../../include/gpx_sweep.h"
@@ -2416,6 +2417,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 
 /* the *_dev calls of the wire, election, scan, sweep, timer, journal, image and checkpoint families: their scratch, argument checks and launches */
 #include "gpx_ctl_args.inc"
+#include "gpx_ctl_block.inc"
 #include "gpx_wire_dev.inc"
 #include "gpx_elect_dev.inc"
 #include "gpx_scan_dev.inc"

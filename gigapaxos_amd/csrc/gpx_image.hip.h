@@ -15,14 +15,13 @@
 //                 own (it would live in scratch): words go straight from global memory to LDS or back.  A ring entry
 //                 of the import that straddles two chunks carries its first words in three named registers.
 //
-// EXPORT is the three launches of gpx_sweep.hip.h with a per-entry weight of 1 or 2 rows:
-//   k_image_tile     one workgroup per GPX_IMAGE_TILE entries: a live entry parks its group (bit 31: it is running for
-//                    coordinator and needs a continuation row) at its rank inside the tile; tile_live / tile_rows.
-//   k_image_offsets  ONE workgroup: exclusive prefixes of tile_rows (tile_off) and tile_live (tile_goff), and the
-//                    counts; where `cap` cuts a tile it walks that tile's parked entries for the exact n_done.
-//   k_image_move     one workgroup per tile: the row offset of parked entry j is tile_off + the prefix of the weights
-//                    before it; it is written iff ALL its rows end at or before cap.  Offsets include the rows of an
-//                    entry that does not fit, so nothing after it fits either: the groups written are a prefix.
+// EXPORT is the three launches of gpx_compact.hip.h with a per-entry weight of 1 or 2 rows:
+//   k_image_tile     one lane per entry: a live entry parks its group (bit 31: it is running for coordinator and needs
+//                    a continuation row); tile_live / tile_rows.
+//   k_image_offsets  exclusive prefixes of tile_rows (tile_off) and tile_live (tile_goff), and the counts; where `cap`
+//                    cuts a tile it walks that tile's parked entries for the exact n_done (cap_cut).
+//   k_image_move     the row offset of parked entry j is tile_off + the prefix of the weights before it; it is written
+//                    iff ALL its rows end at or before cap (weighted_fits): the groups written are a prefix.
 //                    Under GPX_IMG_EVICT a lane retires its group after it has read the last word of it.
 // IMPORT is two launches over tiles of GPX_IMAGE_TILE rows:
 //   k_image_rows<false>  judges every row by itself (header, ring indices, c_pcount, every word canonical,
@@ -32,10 +31,9 @@
 //                        and, for the groups taken, every state word: the election words (c_wait, co_ring, co_handle,
 //                        p_handle) from the continuation row, or zero where there is none and they are allocated.
 //
-// SCRATCH INVARIANT, as in gpx_sweep.hip.h: a call reads only scratch words it wrote itself.  k_image_offsets reads
-// tile_live / tile_rows [0, ntiles) (written unconditionally by each tile's workgroup) and parked entries below
-// tile_live of the cut tile; k_image_move reads tile_live[t], tile_off[t] and parked entries j < tile_live[t];
-// k_image_rows<true> reads desc / src of rows < n_rows, all written by k_image_rows<false> of the same call.
+// SCRATCH INVARIANT (gpx_compact.hip.h), and beyond the export's three launches: k_image_offsets reads parked entries
+// below tile_live of the cut tile; k_image_rows<true> reads desc / src of rows < n_rows, all written by
+// k_image_rows<false> of the same call.
 //
 // Bounds.  A parked entry sits at tile * GPX_IMAGE_TILE + rank, rank < GPX_IMAGE_TILE; the host refuses n above the
 // entries the parked column holds and n_rows above desc / src.  A group number indexes state only after it has been
@@ -48,7 +46,6 @@
 #pragma once
 
 #define GPX_IMAGE_TILE GPX_BLOCK
-#define GPX_IMAGE_WAVES (GPX_BLOCK / 64)
 #define GPX_IMAGE_CW 32
 #define GPX_IMAGE_LS 36
 #define GPX_IMAGE_PREP 0x80000000u
@@ -118,9 +115,8 @@ __device__ __forceinline__ void image_ending(int32_t base, int32_t ew_shift, int
 
 __global__ __launch_bounds__(GPX_BLOCK) void k_image_tile(DevState S, int32_t n, const int32_t* __restrict__ gidx,
                                                          int32_t g_base, ImageMem M) {
-  __shared__ int32_t w_cnt[2][GPX_IMAGE_WAVES];
+  __shared__ int32_t w_cnt[2][GPX_COMPACT_WAVES];
   const int32_t t0 = (int32_t)blockIdx.x * GPX_IMAGE_TILE;
-  const int32_t wave = (int32_t)threadIdx.x >> 6;
   const int64_t i = (int64_t)t0 + (int32_t)threadIdx.x;
   bool live = false, prep = false;
   int32_t g = 0;
@@ -132,85 +128,41 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_tile(DevState S, int32_t n,
       prep = live && (gf & GF_PREPARING) && S.c_wait;
     }
   }
-  const unsigned long long ml = __ballot(live), mp = __ballot(prep);
-  if ((threadIdx.x & 63) == 0) {
-    w_cnt[0][wave] = __popcll(ml);
-    w_cnt[1][wave] = __popcll(mp);
-  }
-  __syncthreads();
-  int32_t before = 0, total = 0, total_p = 0;
-#pragma unroll
-  for (int32_t q = 0; q < GPX_IMAGE_WAVES; q++) {
-    const int32_t c = w_cnt[0][q];
-    before += q < wave ? c : 0;
-    total += c;
-    total_p += w_cnt[1][q];
-  }
-  if (live) M.park[t0 + before + sweep_rank_below(ml)] = (int32_t)((uint32_t)g | (prep ? GPX_IMAGE_PREP : 0u));
+  const TileCount<2> c = tile_count(w_cnt, {live, prep});
+  if (live) M.park[t0 + c.before[0]] = (int32_t)((uint32_t)g | (prep ? GPX_IMAGE_PREP : 0u));
   if (threadIdx.x == 0) {
-    M.tile_live[blockIdx.x] = total;
-    M.tile_rows[blockIdx.x] = total + total_p;
+    M.tile_live[blockIdx.x] = c.total[0];
+    M.tile_rows[blockIdx.x] = c.total[0] + c.total[1];
   }
 }
 
+/* the weight of parked entry e of the exports: a group that is running for coordinator has a continuation row */
+__device__ __forceinline__ int32_t image_weight(int32_t e) { return e < 0 ? 2 : 1; }
+
 __global__ __launch_bounds__(GPX_BLOCK) void k_image_offsets(int32_t ntiles, ImageMem M, int32_t cap,
                                                             ImageCounts* __restrict__ counts) {
-  __shared__ int32_t w_sum[2][GPX_IMAGE_WAVES];
-  __shared__ int32_t s_cut, s_nd, s_nr;
-  const int32_t lane = (int32_t)threadIdx.x & 63, wave = (int32_t)threadIdx.x >> 6;
-  if (threadIdx.x == 0) {
-    s_cut = -1;
-    s_nd = 0;
-    s_nr = 0;
-  }
-  int32_t run_r = 0, run_l = 0;
-  for (int32_t tb = 0; tb < ntiles; tb += GPX_BLOCK) {
-    const int32_t t = tb + (int32_t)threadIdx.x;
-    const int32_t r = t < ntiles ? M.tile_rows[t] : 0;
-    const int32_t l = t < ntiles ? M.tile_live[t] : 0;
-    const int32_t ir = wave_incscan(r), il = wave_incscan(l);
-    __syncthreads(); /* w_sum of the round before has been read; s_cut is initialised */
-    if (lane == 63) {
-      w_sum[0][wave] = ir;
-      w_sum[1][wave] = il;
-    }
-    __syncthreads();
-    int32_t br = 0, bl = 0, tr = 0, tl = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_IMAGE_WAVES; q++) {
-      br += q < wave ? w_sum[0][q] : 0;
-      bl += q < wave ? w_sum[1][q] : 0;
-      tr += w_sum[0][q];
-      tl += w_sum[1][q];
-    }
-    if (t < ntiles) {
-      const int32_t off = run_r + br + ir - r;
-      M.tile_off[t] = off;
-      M.tile_goff[t] = run_l + bl + il - l;
-      if (off <= cap && (int64_t)off + r > cap) s_cut = t; /* at most one tile: offsets ascend */
-    }
-    run_r += tr;
-    run_l += tl;
-  }
-  __syncthreads();
+  __shared__ int32_t s_cut;
+  if (threadIdx.x == 0) s_cut = -1;
+  int32_t sum[2]; /* rows, live */
+  tile_offsets<2, 0>(
+      ntiles, [&](int32_t t, int32_t(&v)[2]) { v[0] = M.tile_rows[t], v[1] = M.tile_live[t]; },
+      [&](int32_t t, const int32_t(&off)[2], const int32_t(&v)[2]) {
+        M.tile_off[t] = off[0];
+        M.tile_goff[t] = off[1];
+        if (off[0] <= cap && (int64_t)off[0] + v[0] > cap) s_cut = t; /* at most one tile: offsets ascend */
+      },
+      sum);
+  __syncthreads(); /* s_cut: initialised (ntiles == 0: no barrier above) or stored */
   const int32_t cut = s_cut; /* the same in every lane */
-  int32_t n_done = run_l, n_rows_done = run_r;
+  int32_t n_done = sum[1], n_rows_done = sum[0];
   if (cut >= 0) {
     /* the tile `cap` cuts: the entries of it that still fit (its own words: written above, by this workgroup) */
     const int32_t c = M.tile_live[cut], off = M.tile_off[cut], j = (int32_t)threadIdx.x;
-    const int32_t e = j < c ? M.park[(int64_t)cut * GPX_IMAGE_TILE + j] : 0;
-    const int32_t w = j < c ? (e < 0 ? 2 : 1) : 0;
-    int32_t tot = 0;
-    const int32_t pre = block_exscan(w, &tot);
-    if (j < c && (int64_t)off + pre + w <= cap) {
-      atomicAdd(&s_nd, 1);
-      atomicAdd(&s_nr, w);
-    }
-    __syncthreads();
-    n_done = M.tile_goff[cut] + s_nd;
-    n_rows_done = off + s_nr;
+    const CapCut f = cap_cut(off, j < c ? image_weight(M.park[(int64_t)cut * GPX_IMAGE_TILE + j]) : 0, cap);
+    n_done = M.tile_goff[cut] + f.n;
+    n_rows_done = off + f.rows;
   }
-  if (threadIdx.x == 0) *counts = ImageCounts{run_l, run_r, n_done, n_rows_done};
+  if (threadIdx.x == 0) *counts = ImageCounts{sum[1], sum[0], n_done, n_rows_done};
 }
 
 /* lane's words of chunk [lo, lo + CW) of the MAIN row of live group g into dst (zeroed): canonical.
@@ -357,10 +309,8 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_image_move(DevState S, ImageMem M
   const int32_t e = j < c ? M.park[(int64_t)blockIdx.x * GPX_IMAGE_TILE + j] : 0;
   const int32_t g = (int32_t)((uint32_t)e & ~GPX_IMAGE_PREP);
   const bool prep = e < 0;
-  const int32_t w = j < c ? (prep ? 2 : 1) : 0;
-  int32_t tot = 0;
-  const int32_t pre = block_exscan(w, &tot);
-  const bool fits = j < c && (int64_t)off + pre + w <= cap;
+  int32_t pre = 0;
+  const bool fits = weighted_fits(off, j < c ? image_weight(e) : 0, cap, &pre);
   s_main[j] = fits ? off + pre : -1;
   s_cont[j] = fits && prep ? off + pre + 1 : -1;
   const int any_cont = __syncthreads_or(fits && prep);

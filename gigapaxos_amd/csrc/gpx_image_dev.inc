@@ -1,6 +1,6 @@
 // Device-pointer side of the group images (include/gpx_image.h; kernels in gpx_image.hip.h): the argument checks, the
 // scratch, gpx_image_stride and the two *_dev calls; the host-pointer twins: gpx_image_host.inc.
-// Needs: the engine and the kernels of gpx_engine.hip, scan_max_n (gpx_scan_dev.inc), elect_init (gpx_elect_dev.inc).
+// Needs: the engine and the kernels of gpx_engine.hip, gpx_ctl_block.inc, elect_init (gpx_elect_dev.inc).
 
 namespace {
 
@@ -30,38 +30,21 @@ int image_import_args(const gpx_engine* h, int32_t n_rows, const void* rows, int
 
 inline size_t image_stride_bytes(const gpx_engine* e) { return (size_t)image_stride_words(e->cfg.kmax, e->cfg.window) * 4; }
 
-/* The export's parked entries and per-tile words, the import's row words and the host twins' counts: ONE block,
- * allocated by the first call of either kind.  Not cleared: a call reads only what it wrote (gpx_image.hip.h).  A
- * failed allocation leaves nothing behind and the engine usable. */
+/* The export's parked entries and per-tile words, the import's row words and the host twins' counts: ONE block
+ * (ctl_block), allocated by the first call of either kind.  Not cleared. */
 int image_init(gpx_engine* e) {
   if (e->img_counts) return GPX_OK;
-  const size_t tiles = std::max<size_t>(((size_t)scan_max_n(e) + GPX_IMAGE_TILE - 1) / GPX_IMAGE_TILE, 1);
-  const size_t cap = tiles * GPX_IMAGE_TILE;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_pk = up(cap * 4), b_tl = up(tiles * 4), b_ds = up(2 * cap), b_sr = up(2 * cap * 4);
-  char* base = nullptr;
-  int rc = dev_alloc(e, &base, b_pk + 4 * b_tl + b_ds + b_sr + 256, false);
-  if (rc != GPX_OK) return rc;
+  const size_t tiles = ctl_tiles(e, GPX_IMAGE_TILE), cap = tiles * GPX_IMAGE_TILE;
   ImageMem& M = e->img;
-  char* p = base;
-  M.park = (int32_t*)p, p += b_pk;
-  M.tile_live = (int32_t*)p, p += b_tl;
-  M.tile_rows = (int32_t*)p, p += b_tl;
-  M.tile_off = (int32_t*)p, p += b_tl;
-  M.tile_goff = (int32_t*)p, p += b_tl;
-  M.desc = (uint8_t*)p, p += b_ds;
-  M.src = (int32_t*)p, p += b_sr;
-  e->img_counts = (ImageCounts*)p; /* last: the marker */
-  return GPX_OK;
+  return ctl_block(e,
+                   {ctl_col(&M.park, cap), ctl_col(&M.tile_live, tiles), ctl_col(&M.tile_rows, tiles),
+                    ctl_col(&M.tile_off, tiles), ctl_col(&M.tile_goff, tiles), ctl_col(&M.desc, 2 * cap),
+                    ctl_col(&M.src, 2 * cap), ctl_col(&e->img_counts, 1)},
+                   false);
 }
 
-/* what a call needs of the engine: the size limit, an engine an exchange kernel gave up on, the scratch */
-int image_open(gpx_engine* h, int64_t n, int64_t limit) {
-  if (n > limit) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  return image_init(h);
-}
+/* what a call needs of the engine: at most `limit` entries or rows, then ctl_open's checks and the scratch */
+int image_open(gpx_engine* h, int64_t n, int64_t limit) { return ctl_open(h, n, limit, image_init); }
 
 inline ImageIdle image_idle(const gpx_engine* h) { return ImageIdle{h->sweep.sig, h->sweep.age}; }
 inline NameCopies image_names(const gpx_engine* h) { return NameCopies{h->N.rows, (uint8_t*)h->N.tab}; }
@@ -70,7 +53,7 @@ inline NameCopies image_names(const gpx_engine* h) { return NameCopies{h->N.rows
 int image_export_run(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t g_base, int32_t flags, int32_t cap,
                      void* o_rows, gpx_image_counts* counts) {
   h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n + GPX_IMAGE_TILE - 1) / GPX_IMAGE_TILE);
+  const int ntiles = tiles_for(n, GPX_IMAGE_TILE);
   if (ntiles) LAUNCH(h, "k_image_tile", k_image_tile, ntiles, h->S, n, gidx, g_base, h->img);
   LAUNCH(h, "k_image_offsets", k_image_offsets, 1, (int32_t)ntiles, h->img, cap, (ImageCounts*)counts);
   if (ntiles && cap > 0)
@@ -82,7 +65,7 @@ int image_export_run(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t g_ba
 /* the two launches of an import (the election arrays: the caller's business) */
 int image_import_run(gpx_engine* h, int32_t n_rows, const void* rows, const int32_t* gidx, uint8_t* status) {
   h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n_rows + GPX_IMAGE_TILE - 1) / GPX_IMAGE_TILE);
+  const int ntiles = tiles_for(n_rows, GPX_IMAGE_TILE);
   if (!ntiles) return GPX_OK;
   LAUNCH(h, "k_image_check", k_image_rows<false>, ntiles, h->S, h->img, image_names(h), image_idle(h), n_rows,
          (const int32_t*)rows, gidx, status);

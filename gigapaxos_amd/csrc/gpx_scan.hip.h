@@ -1,34 +1,17 @@
 // Table scans that return only their hits (include/gpx_scan.h): election, poke and gap scan with the
 // hits compacted on the device in entry order, the count left in device memory.
 //
-// A call is three launches on one stream, and no workgroup ever waits for another one:
+// The three launches, the scratch invariant and the bounds argument: gpx_compact.hip.h.  What is the scans' own:
 //
-//   k_scan_*_tile    one workgroup per GPX_SCAN_TILE consecutive entries, consecutive lanes on consecutive
-//                    entries (the state columns stay coalesced dword streams, as in the dense kernels).  Every
-//                    entry is evaluated ONCE, by the same per-group function the dense kernel calls
-//                    (election_scan_row / poke_scan_row / gap_scan_row).  A hit's rank inside the tile comes from
-//                    the wave's ballot (mbcnt below the lane), a per-wave prefix in LDS and the hits of the
-//                    tile's earlier passes; its row is parked at scratch[tile base + rank].  The tile's hit and
+//   k_scan_*_tile    GPX_SCAN_TILE entries in passes of GPX_BLOCK; the state columns stay coalesced dword streams, as in
+//                    the dense kernels.  An entry is evaluated by the same per-group function the dense kernel calls
+//                    (election_scan_row / poke_scan_row / gap_scan_row); a hit's row is parked.  The tile's hit and
 //                    no-group counts go to tile_hits[tile] / tile_nog[tile].
-//   k_scan_offsets   ONE workgroup: exclusive prefix of tile_hits into tile_off, the sums into *counts.
-//   k_scan_*_move    one workgroup per tile: parked row j of tile t goes to output entry tile_off[t] + j while
-//                    that is below cap.  Only hits move; nothing is evaluated twice.
-//
-// The order between the steps is the stream's.  There are no look-back words, no arrival counters and no
-// assumption about residency, so this path adds nothing to the epochs of DESIGN.md 3.3 and nothing that can
-// starve on a shared device.
-//
-// SCRATCH INVARIANT: every scratch word a call reads is one the SAME call wrote.  k_scan_offsets reads
-// tile_hits / tile_nog [0, ntiles): each written (unconditionally) by its tile's workgroup.  k_scan_*_move reads
-// tile_hits[t], tile_off[t] (written by k_scan_offsets for every t < ntiles) and parked rows j < tile_hits[t] of
-// tile t: exactly the rows that tile's workgroup wrote.  Nothing is cleared between calls and nothing needs to be.
-//
-// Bounds: a parked row sits at tile * GPX_SCAN_TILE + rank with rank < GPX_SCAN_TILE, and the scratch columns
-// hold max(max_groups, max_batch) entries rounded up to whole tiles; the host refuses a larger n.
+//   k_scan_offsets   tile_off = exclusive prefix of tile_hits, the two sums into *counts.
+//   k_scan_*_move    copies the parked row.
 #pragma once
 
 #define GPX_SCAN_TILE_ 1024 /* == GPX_SCAN_TILE of include/gpx_scan.h (checked in gpx_scan_dev.inc) */
-#define GPX_SCAN_WAVES (GPX_BLOCK / 64)
 
 struct ScanCounts { /* == gpx_scan_counts */
   int32_t n_hits, n_nogroup, reserved[2];
@@ -137,17 +120,11 @@ struct ScanGap {
   }
 };
 
-/* lanes of this wave below the caller's whose bit is set in m */
-__device__ __forceinline__ int32_t scan_rank_below(unsigned long long m) {
-  return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 template <class E>
 __global__ __launch_bounds__(GPX_BLOCK) void k_scan_tile(DevState S, int32_t n, const int32_t* __restrict__ gidx,
                                                         E ev, ScanScratch X) {
-  __shared__ int32_t w_hits[2][GPX_SCAN_WAVES], w_nog[2][GPX_SCAN_WAVES];
+  __shared__ int32_t w_cnt[2][2][GPX_COMPACT_WAVES]; /* two sets, used alternately: one barrier per pass */
   const int32_t t0 = (int32_t)blockIdx.x * GPX_SCAN_TILE_; /* n <= 2^31 - 1: the last tile's base fits */
-  const int32_t wave = (int32_t)threadIdx.x >> 6;
   int32_t base = 0, nog = 0; /* the tile's hits / no-group entries of the passes so far: the same in every lane */
 #pragma unroll 1 /* one copy of the evaluation: unrolled, the state pointers of four copies spill scalar registers */
   for (int32_t pass = 0; pass < GPX_SCAN_TILE_ / GPX_BLOCK; pass++) {
@@ -161,23 +138,10 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_scan_tile(DevState S, int32_t n, 
       hit = ev.hit(r);
       ng = ev.nogroup(r);
     }
-    const unsigned long long mh = __ballot(hit), mn = __ballot(ng);
-    /* two sets of LDS words, used alternately: one barrier per pass */
-    if ((threadIdx.x & 63) == 0) {
-      w_hits[pass & 1][wave] = __popcll(mh);
-      w_nog[pass & 1][wave] = __popcll(mn);
-    }
-    __syncthreads();
-    int32_t before = 0, total = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_SCAN_WAVES; q++) {
-      const int32_t c = w_hits[pass & 1][q];
-      before += q < wave ? c : 0;
-      total += c;
-      nog += w_nog[pass & 1][q];
-    }
-    if (hit) ev.park(X, t0 + base + before + scan_rank_below(mh), g, r);
-    base += total;
+    const TileCount<2> c = tile_count(w_cnt[pass & 1], {hit, ng});
+    if (hit) ev.park(X, t0 + base + c.before[0], g, r);
+    base += c.total[0];
+    nog += c.total[1];
   }
   if (threadIdx.x == 0) {
     X.tile_hits()[blockIdx.x] = base;
@@ -187,46 +151,17 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_scan_tile(DevState S, int32_t n, 
 
 /* one workgroup: tile_off = exclusive prefix of tile_hits, *counts = the sums */
 __global__ __launch_bounds__(GPX_BLOCK) void k_scan_offsets(int32_t ntiles, ScanScratch X, ScanCounts* __restrict__ counts) {
-  __shared__ int32_t w_sum[GPX_SCAN_WAVES], w_nog[GPX_SCAN_WAVES];
-  const int32_t lane = (int32_t)threadIdx.x & 63, wave = (int32_t)threadIdx.x >> 6;
-  int32_t running = 0, nog = 0;
-  for (int32_t t0 = 0; t0 < ntiles; t0 += GPX_BLOCK) {
-    const int32_t t = t0 + (int32_t)threadIdx.x;
-    const int32_t c = t < ntiles ? X.tile_hits()[t] : 0;
-    int32_t ng = t < ntiles ? X.tile_nog()[t] : 0;
-    int32_t inc = c; /* inclusive prefix within the wave */
-#pragma unroll
-    for (int32_t d = 1; d < 64; d <<= 1) {
-      const int32_t v = __shfl_up(inc, d);
-      const int32_t u = __shfl_xor(ng, d);
-      if (lane >= d) inc += v;
-      ng += u; /* butterfly: every lane ends with the wave's sum */
-    }
-    if (lane == 63) {
-      w_sum[wave] = inc;
-      w_nog[wave] = ng;
-    }
-    __syncthreads();
-    int32_t before = 0, total = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_SCAN_WAVES; q++) {
-      before += q < wave ? w_sum[q] : 0;
-      total += w_sum[q];
-      nog += w_nog[q];
-    }
-    if (t < ntiles) X.tile_off()[t] = running + before + inc - c;
-    running += total;
-    __syncthreads(); /* w_sum is rewritten by the next round */
-  }
-  if (threadIdx.x == 0) *counts = ScanCounts{running, nog, {0, 0}};
+  int32_t sum[2];
+  tile_offsets<1, 1>(
+      ntiles, [&](int32_t t, int32_t(&v)[2]) { v[0] = X.tile_hits()[t], v[1] = X.tile_nog()[t]; },
+      [&](int32_t t, const int32_t(&off)[1], const int32_t(&)[2]) { X.tile_off()[t] = off[0]; }, sum);
+  if (threadIdx.x == 0) *counts = ScanCounts{sum[0], sum[1], {0, 0}};
 }
 
 template <class E>
 __global__ __launch_bounds__(GPX_BLOCK) void k_scan_move(ScanScratch X, ScanOut O, int32_t cap) {
-  const int32_t c = X.tile_hits()[blockIdx.x], off = X.tile_off()[blockIdx.x];
-  const int32_t lim = min(c, cap - off); /* off <= n_hits <= 2^31 - 1, cap >= 0: no overflow */
-  const int32_t p0 = (int32_t)blockIdx.x * GPX_SCAN_TILE_;
-  for (int32_t j = (int32_t)threadIdx.x; j < lim; j += GPX_BLOCK) E::move(X, p0 + j, O, off + j);
+  const MoveSpan m = move_span<GPX_SCAN_TILE_>(X.tile_hits(), X.tile_off(), cap);
+  for (int32_t j = (int32_t)threadIdx.x; j < m.lim; j += GPX_BLOCK) E::move(X, m.p0 + j, O, m.off + j);
 }
 
 /* gpx_election_begin for the first min(counts->n_hits, cap) entries: k_election_begin's effect entry for entry */

@@ -1,6 +1,6 @@
 // Device-pointer side of the hit-compacting scans (include/gpx_scan.h; kernels in gpx_scan.hip.h): the scratch, the
 // engine-side checks and the *_dev calls; the host-pointer twins: gpx_scan_host.inc.
-// Needs: the engine and the kernels of gpx_engine.hip, elect_init (gpx_elect_dev.inc), gpx_ctl_args.inc.
+// Needs: the engine and the kernels of gpx_engine.hip, elect_init (gpx_elect_dev.inc), gpx_ctl_args.inc, gpx_ctl_block.inc.
 
 namespace {
 
@@ -8,40 +8,27 @@ static_assert(GPX_SCAN_TILE == GPX_SCAN_TILE_, "include/gpx_scan.h and gpx_scan.
 static_assert(GPX_SCAN_TILE % GPX_BLOCK == 0, "a tile is whole passes of a workgroup");
 static_assert(sizeof(gpx_scan_counts) == 16 && sizeof(ScanCounts) == 16, "gpx_scan_counts is 16 bytes");
 
-inline int64_t scan_max_n(const gpx_engine* e) { return std::max<int64_t>(e->cfg.max_groups, e->cfg.max_batch); }
-
-/* The parked rows, the per-tile words and the host twins' counts: ONE block, allocated by the first scan and sized
- * once for max(max_groups, max_batch) entries in whole tiles.  Not cleared: a call reads only what it wrote
- * (gpx_scan.hip.h).  A failed allocation leaves nothing behind and the engine usable. */
+/* The parked rows, the per-tile words and the host twins' counts: ONE block (ctl_block), allocated by the first scan
+ * and sized once for max(max_groups, max_batch) entries in whole tiles.  Not cleared. */
 int scan_init(gpx_engine* e) {
   if (e->scan_counts) return GPX_OK;
-  const size_t tiles = ((size_t)scan_max_n(e) + GPX_SCAN_TILE - 1) / GPX_SCAN_TILE;
-  const size_t cap = std::max<size_t>(tiles, 1) * GPX_SCAN_TILE;
-  const size_t tl = (std::max<size_t>(tiles, 1) * 4 + 255) & ~(size_t)255;
+  const size_t tiles = ctl_tiles(e, GPX_SCAN_TILE), cap = tiles * GPX_SCAN_TILE, tl = (tiles * 4 + 255) & ~(size_t)255;
   if (cap > UINT32_MAX) return GPX_ECAPACITY;
-  char* base = nullptr;
-  int rc = dev_alloc(e, &base, 26 * cap + 3 * tl + 256, false); /* ScanScratch's layout, then the counts */
-  if (rc != GPX_OK) return rc;
-  e->scan = ScanScratch{base, (uint32_t)cap, (uint32_t)tl};
-  e->scan_counts = (ScanCounts*)(base + 26 * cap + 3 * tl); /* last: the marker */
-  return GPX_OK;
+  ScanScratch X{nullptr, (uint32_t)cap, (uint32_t)tl};
+  int rc = ctl_block(e, {ctl_col(&X.base, 26 * cap + 3 * tl) /* ScanScratch's layout */, ctl_col(&e->scan_counts, 1)}, false);
+  if (rc == GPX_OK) e->scan = X;
+  return rc;
 }
 
-/* what a scan needs of the engine (its arguments: scan_args / scan_lists, gpx_ctl_args.inc): the size limit, an engine
- * an exchange kernel gave up on, the scratch */
-int scan_open(gpx_engine* h, int32_t n) {
-  if ((int64_t)n > scan_max_n(h)) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  return scan_init(h);
-}
+/* ctl_open for this family, under the name its host-pointer twin calls */
+int scan_open(gpx_engine* h, int32_t n) { return ctl_open(h, n, scan_max_n(h), scan_init); }
 
 /* the three launches of one scan on the back-end stream (gpx_scan.hip.h) */
 template <class E>
 int scan_run(gpx_engine* h, const char* tile_name, const char* move_name, int32_t n, const int32_t* gidx, const E& ev,
              int32_t cap, const ScanOut& O, gpx_scan_counts* counts) {
   h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n + GPX_SCAN_TILE - 1) / GPX_SCAN_TILE);
+  const int ntiles = tiles_for(n, GPX_SCAN_TILE);
   if (ntiles) LAUNCH(h, tile_name, (k_scan_tile<E>), ntiles, h->S, n, gidx, ev, h->scan);
   LAUNCH(h, "k_scan_offsets", k_scan_offsets, 1, (int32_t)ntiles, h->scan, (ScanCounts*)counts);
   if (ntiles && cap > 0) LAUNCH(h, move_name, (k_scan_move<E>), ntiles, h->scan, O, cap);

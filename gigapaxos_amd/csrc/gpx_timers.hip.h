@@ -1,42 +1,32 @@
 // Retransmission sweep (include/gpx_timers.h): find the ACCEPTs and PREPAREs that have waited for replies longer than
 // their threshold, hand back their poke rows compacted in entry order and re-arm exactly the ones handed back.
 //
-// A call is three launches on one stream, the scheme of gpx_scan.hip.h and gpx_sweep.hip.h; no workgroup ever waits
-// for another one:
+// The three launches, the scratch invariant and the bounds argument: gpx_compact.hip.h.  What is this sweep's own:
 //
-//   k_rtx_tile     one workgroup per GPX_RTX_TILE consecutive entries, consecutive lanes on consecutive entries.  The
-//                  entry's three timer words (key, since, count) are loaded first, then the entry is evaluated ONCE by
-//                  poke_scan_row (gpx_elect.hip.h, the function k_poke_scan calls).  A wait with a new key is armed
-//                  here, a group that waits for nothing is disarmed here: neither depends on `cap`.  A wait whose key
-//                  is the stored one and whose age exceeds its threshold is a hit and parks (group, waited, count) at
-//                  its rank inside the tile.  The tile's hit, no-group and waiting counts go to tile_hits / tile_nog /
-//                  tile_wait [tile], unconditionally.
-//   k_rtx_offsets  ONE workgroup: exclusive prefix of tile_hits into tile_off, the sums and n_fired into *counts.
-//   k_rtx_move     one workgroup per tile: parked hit j of tile t is output entry o = tile_off[t] + j while o < cap.
-//                  The lane evaluates its group's poke row again (no group state has changed since the first launch:
-//                  the stream orders the three, and only timer words are written), writes the columns and then -
-//                  unless the call only peeks - re-arms the group: count + 1 saturating at 255, since = now.  THE ONLY
-//                  PLACE A HIT'S WORDS CHANGE: which hits fit `cap` is known only after the offsets.
+//   k_rtx_tile     GPX_RTX_TILE entries in passes of GPX_BLOCK.  The entry's three timer words (key, since, count) are
+//                  loaded first, then the entry is evaluated by poke_scan_row (gpx_elect.hip.h, the function k_poke_scan
+//                  calls).  A wait with a new key is armed here, a group that waits for nothing is disarmed here: neither
+//                  depends on `cap`.  A wait whose key is the stored one and whose age exceeds its threshold is a hit
+//                  and parks (group, waited, count).  The tile's hit, no-group and waiting counts go to tile_hits /
+//                  tile_nog / tile_wait [tile].
+//   k_rtx_offsets  tile_off = exclusive prefix of tile_hits, the sums and n_fired into *counts.
+//   k_rtx_move     the lane evaluates its group's poke row again (no group state has changed since the first launch: the
+//                  stream orders the three, and only timer words are written), writes the columns and then - unless the
+//                  call only peeks - re-arms the group: count + 1 saturating at 255, since = now.  THE ONLY PLACE A
+//                  HIT'S WORDS CHANGE: which hits fit `cap` is known only after the offsets.
 //
 // The thresholds travel in the kernel arguments (RtxCfg, 260 bytes) and are read with a lane-uniform index: the loop
 // over the steps is the same in every lane, a lane keeps the entry of its own step.
 //
-// SCRATCH INVARIANT, as in gpx_scan.hip.h: every scratch word a call reads is one the SAME call wrote.  k_rtx_offsets
-// reads tile_hits / tile_nog / tile_wait [0, ntiles): each written unconditionally by its tile's workgroup.  k_rtx_move
-// reads tile_hits[t], tile_off[t] (written for every t < ntiles) and parked entries j < tile_hits[t] of tile t.  The
-// timer words are not scratch: they are engine state, zeroed when allocated, and only these kernels touch them.
-//
-// Bounds: a parked entry sits at tile * GPX_RTX_TILE + rank with rank < GPX_RTX_TILE; the parked columns hold
-// max(max_groups, max_batch) entries rounded up to whole tiles and the host refuses a larger n.  The timer words are
-// indexed by a group number only after it has been checked against S.G; a parked group is one of those (poke_scan_row
-// answers GPX_S_NOGROUP for every other).  An output index is below min(n_hits, cap).
+// The timer words are not scratch: they are engine state, zeroed when allocated, and only these kernels touch them.
+// They are indexed by a group number only after it has been checked against S.G; a parked group is one of those
+// (poke_scan_row answers GPX_S_NOGROUP for every other).
 //
 // Distinct entries (a precondition, as for the pause sweep): two entries naming one group would race on its timer
 // words and could both park it.
 #pragma once
 
 #define GPX_RTX_TILE 1024
-#define GPX_RTX_WAVES (GPX_BLOCK / 64)
 #define GPX_RTX_PEEK_ 1       /* == GPX_RTX_PEEK of include/gpx_timers.h (checked in gpx_timers_dev.inc) */
 #define GPX_RTX_MAX_STEPS_ 32 /* == GPX_RTX_MAX_STEPS */
 #define GPX_RTX_COUNT_MAX 255
@@ -61,11 +51,6 @@ struct RtxMem {
   uint8_t* park_count; /* [whole tiles] the count BEFORE this retransmission */
   int32_t *tile_hits, *tile_nog, *tile_wait, *tile_off; /* [tiles] */
 };
-
-/* lanes of this wave below the caller's whose bit is set in m */
-__device__ __forceinline__ int32_t rtx_rank_below(unsigned long long m) {
-  return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 /* The identity of a wait: kind, slot and ballot, never `heard` (a reply does not restart WaitforUtility.initTime).  Odd
  * multipliers and the murmur3 finaliser are bijections: two waits that differ in ONE of the four fields never share a
@@ -95,9 +80,8 @@ __device__ __forceinline__ int32_t rtx_threshold(const RtxCfg& cfg, bool prepare
 template <int KMAX>
 __global__ __launch_bounds__(GPX_BLOCK) void k_rtx_tile(DevState S, int32_t n, const int32_t* __restrict__ gidx,
                                                        int32_t now_ms, RtxCfg cfg, int32_t flags, RtxMem M) {
-  __shared__ int32_t w_cnt[2][3][GPX_RTX_WAVES];
+  __shared__ int32_t w_cnt[2][3][GPX_COMPACT_WAVES]; /* two sets, used alternately: one barrier per pass */
   const int32_t t0 = (int32_t)blockIdx.x * GPX_RTX_TILE; /* n <= 2^31 - 1: the last tile's base fits */
-  const int32_t wave = (int32_t)threadIdx.x >> 6;
   const bool peek = (flags & GPX_RTX_PEEK_) != 0;
   int32_t base = 0, nog = 0, wtg = 0; /* the tile's counts of the passes so far: the same in every lane */
 #pragma unroll 1 /* one copy of the evaluation, as in k_scan_tile */
@@ -135,30 +119,16 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_rtx_tile(DevState S, int32_t n, c
         if (c1 != c0) M.count[g] = (uint8_t)c1;
       }
     }
-    const unsigned long long mh = __ballot(hit), mn = __ballot(ng), mw = __ballot(wt);
-    /* two sets of LDS words, used alternately: one barrier per pass */
-    if ((threadIdx.x & 63) == 0) {
-      w_cnt[pass & 1][0][wave] = __popcll(mh);
-      w_cnt[pass & 1][1][wave] = __popcll(mn);
-      w_cnt[pass & 1][2][wave] = __popcll(mw);
-    }
-    __syncthreads();
-    int32_t before = 0, total = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_RTX_WAVES; q++) {
-      const int32_t c = w_cnt[pass & 1][0][q];
-      before += q < wave ? c : 0;
-      total += c;
-      nog += w_cnt[pass & 1][1][q];
-      wtg += w_cnt[pass & 1][2][q];
-    }
+    const TileCount<3> c = tile_count(w_cnt[pass & 1], {hit, ng, wt});
     if (hit) {
-      const int32_t p = t0 + base + before + rtx_rank_below(mh);
+      const int32_t p = t0 + base + c.before[0];
       M.park_g[p] = g;
       M.park_wait[p] = waited;
       M.park_count[p] = (uint8_t)c0;
     }
-    base += total;
+    base += c.total[0];
+    nog += c.total[1];
+    wtg += c.total[2];
   }
   if (threadIdx.x == 0) {
     M.tile_hits[blockIdx.x] = base;
@@ -170,43 +140,11 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_rtx_tile(DevState S, int32_t n, c
 /* one workgroup: tile_off = exclusive prefix of tile_hits, *counts = the sums and what the move step will re-arm */
 __global__ __launch_bounds__(GPX_BLOCK) void k_rtx_offsets(int32_t ntiles, RtxMem M, int32_t cap, int32_t flags,
                                                           RtxCounts* __restrict__ counts) {
-  __shared__ int32_t w_sum[3][GPX_RTX_WAVES];
-  const int32_t lane = (int32_t)threadIdx.x & 63, wave = (int32_t)threadIdx.x >> 6;
-  int32_t running = 0, nog = 0, wtg = 0;
-  for (int32_t t0 = 0; t0 < ntiles; t0 += GPX_BLOCK) {
-    const int32_t t = t0 + (int32_t)threadIdx.x;
-    const int32_t c = t < ntiles ? M.tile_hits[t] : 0;
-    int32_t ng = t < ntiles ? M.tile_nog[t] : 0;
-    int32_t wt = t < ntiles ? M.tile_wait[t] : 0;
-    int32_t inc = c; /* inclusive prefix within the wave */
-#pragma unroll
-    for (int32_t d = 1; d < 64; d <<= 1) {
-      const int32_t v = __shfl_up(inc, d);
-      const int32_t u = __shfl_xor(ng, d);
-      const int32_t x = __shfl_xor(wt, d);
-      if (lane >= d) inc += v;
-      ng += u; /* butterflies: every lane ends with the wave's sum */
-      wt += x;
-    }
-    if (lane == 63) {
-      w_sum[0][wave] = inc;
-      w_sum[1][wave] = ng;
-      w_sum[2][wave] = wt;
-    }
-    __syncthreads();
-    int32_t before = 0, total = 0;
-#pragma unroll
-    for (int32_t q = 0; q < GPX_RTX_WAVES; q++) {
-      before += q < wave ? w_sum[0][q] : 0;
-      total += w_sum[0][q];
-      nog += w_sum[1][q];
-      wtg += w_sum[2][q];
-    }
-    if (t < ntiles) M.tile_off[t] = running + before + inc - c;
-    running += total;
-    __syncthreads(); /* w_sum is rewritten by the next round */
-  }
-  if (threadIdx.x == 0) *counts = RtxCounts{running, nog, wtg, (flags & GPX_RTX_PEEK_) ? 0 : min(running, cap)};
+  int32_t sum[3];
+  tile_offsets<1, 2>(
+      ntiles, [&](int32_t t, int32_t(&v)[3]) { v[0] = M.tile_hits[t], v[1] = M.tile_nog[t], v[2] = M.tile_wait[t]; },
+      [&](int32_t t, const int32_t(&off)[1], const int32_t(&)[3]) { M.tile_off[t] = off[0]; }, sum);
+  if (threadIdx.x == 0) *counts = RtxCounts{sum[0], sum[1], sum[2], (flags & GPX_RTX_PEEK_) ? 0 : min(sum[0], cap)};
 }
 
 /* the output columns of one call: gpx_poke_scan's row, then the count after this retransmission and the wait */
@@ -223,13 +161,11 @@ struct RtxOut {
 template <int KMAX>
 __global__ __launch_bounds__(GPX_BLOCK) void k_rtx_move(DevState S, RtxMem M, int32_t now_ms, int32_t cap, int32_t flags,
                                                        RtxOut O) {
-  const int32_t c = M.tile_hits[blockIdx.x], off = M.tile_off[blockIdx.x];
-  const int32_t lim = min(c, cap - off); /* off <= n_hits <= 2^31 - 1, cap >= 0: no overflow */
-  const int32_t p0 = (int32_t)blockIdx.x * GPX_RTX_TILE;
-  for (int32_t j = (int32_t)threadIdx.x; j < lim; j += GPX_BLOCK) {
-    const int32_t g = M.park_g[p0 + j], o = off + j;
-    const int32_t c0 = (int32_t)M.park_count[p0 + j], c1 = min(c0 + 1, GPX_RTX_COUNT_MAX);
-    const int32_t waited = M.park_wait[p0 + j];
+  const MoveSpan m = move_span<GPX_RTX_TILE>(M.tile_hits, M.tile_off, cap);
+  for (int32_t j = (int32_t)threadIdx.x; j < m.lim; j += GPX_BLOCK) {
+    const int32_t g = M.park_g[m.p0 + j], o = m.off + j;
+    const int32_t c0 = (int32_t)M.park_count[m.p0 + j], c1 = min(c0 + 1, GPX_RTX_COUNT_MAX);
+    const int32_t waited = M.park_wait[m.p0 + j];
     const PokeRow r = poke_scan_row<KMAX>(S, g); /* what k_rtx_tile saw: nothing has changed since */
     O.gidx[o] = g;
     O.poke[o] = r.poke;

@@ -1,6 +1,6 @@
 // Device-pointer side of the retransmission sweep (include/gpx_timers.h; kernels in gpx_timers.hip.h): the timer words,
 // the argument checks, the back-off table and gpx_retransmit_sweep_dev; the host-pointer twin: gpx_timers_host.inc.
-// Needs: the engine and the kernels of gpx_engine.hip, scan_max_n (gpx_scan_dev.inc).
+// Needs: the engine and the kernels of gpx_engine.hip, gpx_ctl_block.inc.
 
 namespace {
 
@@ -23,49 +23,30 @@ int rtx_args(const gpx_engine* h, int32_t n, const gpx_rtx_cfg* cfg, int32_t fla
   return GPX_OK;
 }
 
-/* The timer words, the parked hits, the per-tile words and the host twin's counts: ONE block, allocated by the first
- * sweep.  Zeroed: the timer words start at "waiting for nothing" (the rest is scratch, of which a call reads only what
- * it wrote).  A failed allocation leaves nothing behind and the engine usable. */
+/* The timer words, the parked hits, the per-tile words and the host twin's counts: ONE block (ctl_block), allocated by
+ * the first sweep.  Zeroed: the timer words start at "waiting for nothing". */
 int rtx_init(gpx_engine* e) {
   if (e->rtx_counts) return GPX_OK;
   const size_t G = (size_t)std::max(e->cfg.max_groups, 1);
-  const size_t tiles = std::max<size_t>(((size_t)scan_max_n(e) + GPX_RTX_TILE - 1) / GPX_RTX_TILE, 1);
-  const size_t cap = tiles * GPX_RTX_TILE;
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_g4 = up(G * 4), b_g1 = up(G), b_p4 = up(cap * 4), b_p1 = up(cap), b_tl = up(tiles * 4);
-  char* base = nullptr;
-  int rc = dev_alloc(e, &base, 2 * b_g4 + b_g1 + 2 * b_p4 + b_p1 + 4 * b_tl + 256, true);
-  if (rc != GPX_OK) return rc;
+  const size_t tiles = ctl_tiles(e, GPX_RTX_TILE), cap = tiles * GPX_RTX_TILE;
   RtxMem& M = e->rtx;
-  char* p = base;
-  M.key = (uint32_t*)p, p += b_g4;
-  M.since = (int32_t*)p, p += b_g4;
-  M.count = (uint8_t*)p, p += b_g1;
-  M.park_g = (int32_t*)p, p += b_p4;
-  M.park_wait = (int32_t*)p, p += b_p4;
-  M.park_count = (uint8_t*)p, p += b_p1;
-  M.tile_hits = (int32_t*)p, p += b_tl;
-  M.tile_nog = (int32_t*)p, p += b_tl;
-  M.tile_wait = (int32_t*)p, p += b_tl;
-  M.tile_off = (int32_t*)p, p += b_tl;
-  e->rtx_counts = (RtxCounts*)p; /* last: the marker */
-  return GPX_OK;
+  return ctl_block(e,
+                   {ctl_col(&M.key, G), ctl_col(&M.since, G), ctl_col(&M.count, G), ctl_col(&M.park_g, cap),
+                    ctl_col(&M.park_wait, cap), ctl_col(&M.park_count, cap), ctl_col(&M.tile_hits, tiles),
+                    ctl_col(&M.tile_nog, tiles), ctl_col(&M.tile_wait, tiles), ctl_col(&M.tile_off, tiles),
+                    ctl_col(&e->rtx_counts, 1)},
+                   true);
 }
 
-/* what the sweep needs of the engine: the size limit, an engine an exchange kernel gave up on, the timer words */
-int rtx_open(gpx_engine* h, int32_t n) {
-  if ((int64_t)n > scan_max_n(h)) return GPX_ECAPACITY;
-  int rc = check_batch(h, 0);
-  if (rc != GPX_OK) return rc;
-  return rtx_init(h);
-}
+/* ctl_open for this family, under the name its host-pointer twin calls */
+int rtx_open(gpx_engine* h, int32_t n) { return ctl_open(h, n, scan_max_n(h), rtx_init); }
 
 /* the three launches (gpx_timers.hip.h) on the back-end stream */
 template <int KMAX>
 int rtx_run(gpx_engine* h, int32_t n, const int32_t* gidx, int32_t now_ms, const RtxCfg& cfg, int32_t flags, int32_t cap,
             const RtxOut& O, gpx_rtx_counts* counts) {
   h->stream = h->sB;
-  const int ntiles = (int)(((int64_t)n + GPX_RTX_TILE - 1) / GPX_RTX_TILE);
+  const int ntiles = tiles_for(n, GPX_RTX_TILE);
   if (ntiles) LAUNCH(h, "k_rtx_tile", k_rtx_tile<KMAX>, ntiles, h->S, n, gidx, now_ms, cfg, flags, h->rtx);
   LAUNCH(h, "k_rtx_offsets", k_rtx_offsets, 1, (int32_t)ntiles, h->rtx, cap, flags, (RtxCounts*)counts);
   if (ntiles && cap > 0) LAUNCH(h, "k_rtx_move", k_rtx_move<KMAX>, ntiles, h->S, h->rtx, now_ms, cap, flags, O);

@@ -17,78 +17,9 @@
 #include <thread>
 #include <vector>
 
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-#define __restrict__
-#define GPX_BLOCK 256
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static std::barrier<>* g_block_bar;
-static std::barrier<>* g_wave_bar[4];
-static int32_t g_wave_val[4][64];
-static int32_t g_or;
-static void __syncthreads() { g_block_bar->arrive_and_wait(); }
-static int __syncthreads_or(bool p) {
-  if (threadIdx.x == 0) g_or = 0;
-  __syncthreads();
-  if (p) __atomic_store_n(&g_or, 1, __ATOMIC_SEQ_CST);
-  __syncthreads();
-  const int r = g_or;
-  __syncthreads();
-  return r;
-}
-static unsigned long long __ballot(bool p) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  g_wave_val[w][l] = p;
-  g_wave_bar[w]->arrive_and_wait();
-  unsigned long long m = 0;
-  for (int q = 0; q < 64; q++) m |= (unsigned long long)(g_wave_val[w][q] != 0) << q;
-  g_wave_bar[w]->arrive_and_wait();
-  return m;
-}
-static int32_t shfl_up(int32_t v, int d) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  g_wave_val[w][l] = v;
-  g_wave_bar[w]->arrive_and_wait();
-  const int32_t r = l - d >= 0 ? g_wave_val[w][l - d] : v;
-  g_wave_bar[w]->arrive_and_wait();
-  return r;
-}
-static int __popcll(unsigned long long m) { return __builtin_popcountll(m); }
-static int32_t atomicAdd(int32_t* p, int32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-using std::max;
-using std::min;
+#include "lockstep_runtime.h"
 
-/* stand-ins for what gpx_kernels.hip.h gives the two headers: the same names, the same meaning */
-static int32_t sweep_rank_below(unsigned long long m) { return __builtin_popcountll(m & ((1ull << (threadIdx.x & 63)) - 1ull)); }
-static int32_t wave_incscan(int32_t v) {
-  const int l = threadIdx.x & 63;
-  int32_t x = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int32_t y = shfl_up(x, d);
-    if (l >= d) x += y;
-  }
-  return x;
-}
-static int32_t block_exscan(int32_t v, int32_t* total) {
-  static int32_t wsum[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int32_t x = wave_incscan(v);
-  if (lane == 63) wsum[wid] = x;
-  __syncthreads();
-  int32_t base = 0, tot = 0;
-  for (int w = 0; w < 4; w++) {
-    if (w < wid) base += wsum[w];
-    tot += wsum[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + x - v;
-}
+/* what gpx_kernels.hip.h gives the two headers: the same names, the same meaning */
 struct __attribute__((aligned(16))) I4 { int32_t x, y, z, w; };
 static I4 mk4(int32_t x, int32_t y, int32_t z, int32_t w) { return I4{x, y, z, w}; }
 #define GF_EXISTS 1u
@@ -135,33 +66,10 @@ static void group_retire_apply(const DevState& S, int32_t g, const NameCopies& n
 }
 
 #include "gpx_delta.h"
+#include "gpx_compact.hip.h"
 #include "gpx_image.hip.h"
 #include "gpx_delta.hip.h"
 
-template <class F>
-static void launch(int grid, F body) {
-  std::barrier<> bb(GPX_BLOCK), w0(64), w1(64), w2(64), w3(64);
-  g_block_bar = &bb;
-  g_wave_bar[0] = &w0, g_wave_bar[1] = &w1, g_wave_bar[2] = &w2, g_wave_bar[3] = &w3;
-  std::vector<std::thread> th;
-  for (int t = 0; t < GPX_BLOCK; t++)
-    th.emplace_back([=] {
-      for (int b = 0; b < grid; b++) { /* one workgroup at a time: the static arrays are its LDS */
-        threadIdx = Dim3{(unsigned)t, 0, 0};
-        blockIdx = Dim3{(unsigned)b, 0, 0};
-        body();
-        g_block_bar->arrive_and_wait();
-      }
-    });
-  for (auto& x : th) x.join();
-}
-
-// exact-size heap blocks: AddressSanitizer sees every index past an end
-template <class T> static T* blk(size_t n, int fill) {
-  T* p = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-  memset(p, fill, std::max<size_t>(n, 1) * sizeof(T));
-  return p;
-}
 static void fail(const char* what, const char* msg, long a = 0, long b = 0) {
   printf("%s: %s (%ld, %ld)\n", what, msg, a, b);
   exit(1);

@@ -17,59 +17,17 @@
 #include <thread>
 #include <vector>
 
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-#define __restrict__
-#define GPX_BLOCK 256
+#include "lockstep_runtime.h"
+
 #define GPX_S_OK 0
 #define GPX_S_NOGROUP 1
 #define GPX_S_WINDOW 3
 #define GPX_R_TOLOG 1
 #define GPX_R_STORED 2
 #define GPX_NT_JOURNAL 32
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx, gridDim;
-static std::barrier<>* g_block_bar;
-static std::barrier<>* g_wave_bar[4];
-static long long g_wave_val[4][64];
-static int g_block_val[GPX_BLOCK];
-static void __syncthreads() { g_block_bar->arrive_and_wait(); }
-static int __syncthreads_count(bool p) {
-  g_block_val[threadIdx.x] = p;
-  g_block_bar->arrive_and_wait();
-  int c = 0;
-  for (int q = 0; q < GPX_BLOCK; q++) c += g_block_val[q];
-  g_block_bar->arrive_and_wait();
-  return c;
-}
-static unsigned long long __ballot(bool p) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  g_wave_val[w][l] = p;
-  g_wave_bar[w]->arrive_and_wait();
-  unsigned long long m = 0;
-  for (int q = 0; q < 64; q++) m |= (unsigned long long)(g_wave_val[w][q] != 0) << q;
-  g_wave_bar[w]->arrive_and_wait();
-  return m;
-}
-template <class T> static T shfl_from(T v, int src_lane, bool valid) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  g_wave_val[w][l] = (long long)v;
-  g_wave_bar[w]->arrive_and_wait();
-  const T r = valid ? (T)g_wave_val[w][src_lane] : v;
-  g_wave_bar[w]->arrive_and_wait();
-  return r;
-}
-template <class T> static T __shfl_up(T v, int d) { const int l = threadIdx.x & 63; return shfl_from(v, l - d, l - d >= 0); }
-template <class T> static T __shfl_xor(T v, int d) { const int l = threadIdx.x & 63; return shfl_from(v, l ^ d, true); }
-static int __popcll(unsigned long long m) { return __builtin_popcountll(m); }
 static uint32_t __builtin_amdgcn_alignbyte(uint32_t hi, uint32_t lo, uint32_t s) {
   return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (s & 3)));
 }
-using std::max;
-using std::min;
 // gpx_kernels.hip.h's aggregates and stream helpers, as plain accesses
 struct alignas(16) I4 { int32_t x, y, z, w; };
 static I4 mk4(int32_t x, int32_t y, int32_t z, int32_t w) { return I4{x, y, z, w}; }
@@ -79,31 +37,6 @@ template <int BIT> static void stream_store16(I4* p, I4 v) { *p = v; }
 
 #include "gpx_journal.hip.h"
 
-template <class F>
-static void launch(int grid, F body) {
-  std::barrier<> bb(GPX_BLOCK), w0(64), w1(64), w2(64), w3(64);
-  g_block_bar = &bb;
-  g_wave_bar[0] = &w0, g_wave_bar[1] = &w1, g_wave_bar[2] = &w2, g_wave_bar[3] = &w3;
-  std::vector<std::thread> th;
-  for (int t = 0; t < GPX_BLOCK; t++)
-    th.emplace_back([=] {
-      for (int b = 0; b < grid; b++) { /* one workgroup at a time: the static arrays are its LDS */
-        threadIdx = Dim3{(unsigned)t, 0, 0};
-        blockIdx = Dim3{(unsigned)b, 0, 0};
-        gridDim = Dim3{(unsigned)grid, 1, 1};
-        body();
-        g_block_bar->arrive_and_wait();
-      }
-    });
-  for (auto& x : th) x.join();
-}
-
-// exact-size heap blocks: AddressSanitizer sees every index past an end
-template <class T> static T* blk(size_t n, int fill) {
-  T* p = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-  memset(p, fill, std::max<size_t>(n, 1) * sizeof(T));
-  return p;
-}
 template <class T> static T* blk_of(const std::vector<T>& v) {
   T* p = (T*)malloc(std::max<size_t>(v.size(), 1) * sizeof(T));
   if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));

@@ -227,3 +227,19 @@ def test_compaction_kernels_in_lockstep_emulation_under_asan(tmp_path):
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 20 and all(": ok" in ln for ln in lines), out.stdout
+
+
+def test_compaction_core_in_lockstep_emulation_under_asan(tmp_path):
+    """tests/compact_emulation.cpp: the pieces of gpx_compact.hip.h as they are, one thread per lane, each against a
+    plain loop - the per-pass tile count for 2 and 4 predicates with ragged last passes, the offsets loop for 1 to 3
+    prefixed and 0 to 3 summed words at 0, 1, 255, 256, 257 and 600 tiles, the cap-cut helper with the cap at every
+    position of a tile of mixed weights - every buffer of its exact size under AddressSanitizer."""
+    import subprocess
+
+    exe = str(tmp_path / "compact_emulation")
+    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-pthread", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "gigapaxos_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "compact_emulation.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.strip().splitlines() == ["tile_count: ok", "tile_offsets: ok", "cap_cut: ok"], out.stdout

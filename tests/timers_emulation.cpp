@@ -15,49 +15,7 @@
 #include <thread>
 #include <vector>
 
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __shared__ static
-#define __launch_bounds__(x)
-#define __restrict__
-#define GPX_BLOCK 256
-struct Dim3 { unsigned x, y, z; };
-static thread_local Dim3 threadIdx, blockIdx;
-static std::barrier<>* g_block_bar;
-static std::barrier<>* g_wave_bar[4];
-static int32_t g_wave_val[4][64];
-static void __syncthreads() { g_block_bar->arrive_and_wait(); }
-static unsigned long long __ballot(bool p) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  g_wave_val[w][l] = p;
-  g_wave_bar[w]->arrive_and_wait();
-  unsigned long long m = 0;
-  for (int q = 0; q < 64; q++) m |= (unsigned long long)(g_wave_val[w][q] != 0) << q;
-  g_wave_bar[w]->arrive_and_wait();
-  return m;
-}
-static int32_t shfl_from(int32_t v, int src_lane, bool valid) {
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  g_wave_val[w][l] = v;
-  g_wave_bar[w]->arrive_and_wait();
-  const int32_t r = valid ? g_wave_val[w][src_lane] : v;
-  g_wave_bar[w]->arrive_and_wait();
-  return r;
-}
-static int32_t __shfl_up(int32_t v, int d) { const int l = threadIdx.x & 63; return shfl_from(v, l - d, l - d >= 0); }
-static int32_t __shfl_xor(int32_t v, int d) { const int l = threadIdx.x & 63; return shfl_from(v, l ^ d, true); }
-static uint32_t __builtin_amdgcn_mbcnt_lo(uint32_t m, uint32_t acc) {
-  const int l = threadIdx.x & 63;
-  return acc + __builtin_popcount(l >= 32 ? m : (m & ((1u << l) - 1u)));
-}
-static uint32_t __builtin_amdgcn_mbcnt_hi(uint32_t m, uint32_t acc) {
-  const int l = threadIdx.x & 63;
-  return acc + (l <= 32 ? 0 : __builtin_popcount(m & ((1u << (l - 32)) - 1u)));
-}
-static int __popcll(unsigned long long m) { return __builtin_popcountll(m); }
-using std::max;
-using std::min;
+#include "lockstep_runtime.h"
 
 // ---- the fake engine side: the columns below ARE the groups' poke rows; evals counts the evaluations per group ----
 #define GPX_S_OK 0
@@ -83,32 +41,9 @@ static PokeRow poke_scan_row(const DevState& S, int32_t g) {
   return PokeRow{S.poke[g], (uint8_t)(g & 1), GPX_S_OK, S.slot[g], S.bnum[g], 100 + g % KMAX, S.slot[g] - 1 - g % 3, S.heard[g]};
 }
 
+#include "gpx_compact.hip.h"
 #include "gpx_timers.hip.h"
 
-template <class F>
-static void launch(int grid, F body) {
-  std::barrier<> bb(GPX_BLOCK), w0(64), w1(64), w2(64), w3(64);
-  g_block_bar = &bb;
-  g_wave_bar[0] = &w0, g_wave_bar[1] = &w1, g_wave_bar[2] = &w2, g_wave_bar[3] = &w3;
-  std::vector<std::thread> th;
-  for (int t = 0; t < GPX_BLOCK; t++)
-    th.emplace_back([=] {
-      for (int b = 0; b < grid; b++) { /* one workgroup at a time: the static arrays are its LDS */
-        threadIdx = Dim3{(unsigned)t, 0, 0};
-        blockIdx = Dim3{(unsigned)b, 0, 0};
-        body();
-        g_block_bar->arrive_and_wait();
-      }
-    });
-  for (auto& x : th) x.join();
-}
-
-// exact-size heap blocks: AddressSanitizer sees every index past an end
-template <class T> static T* blk(size_t n, int fill) {
-  T* p = (T*)malloc(std::max<size_t>(n, 1) * sizeof(T));
-  memset(p, fill, std::max<size_t>(n, 1) * sizeof(T));
-  return p;
-}
 
 struct Table { /* one engine: groups, timer words, scratch; and the reference's timer words */
   int32_t G;

@@ -94,6 +94,13 @@ class JournalCounts(C.Structure):
                 ("n_bytes", C.c_int64), ("bytes_done", C.c_int64)]
 
 
+class JournalGcCounts(C.Structure):
+    """struct gpx_journal_gc_counts (include/gpx_journal_gc.h): 64 bytes."""
+    _fields_ = ([(f, C.c_int32) for f in ("n_usable", "n_keep", "n_done", "n_bad", "n_unjudged", "n_runs_done", "unchanged",
+                                          "reserved")]
+                + [(f, C.c_int64) for f in ("keep_bytes", "bytes_done", "named_bytes", "reserved2")])
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -134,6 +141,10 @@ _VP = C.c_void_p
 # out, cap_bytes, cap_entries, the seven row columns, counts
 _JOURNAL_PACK_ARGS = ([C.c_int32, _VP, C.c_int64, C.c_int32] + [_VP] * 9 + [C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int32]
                       + [_VP] * 8)
+# gpx_journal_gc[_dev] after the handle: n, in, in_bytes, in_base, the seven input columns, out_base, flags, out, cap_bytes,
+# cap_entries, verdict, the seven k_* columns, counts
+_JOURNAL_GC_ARGS = ([C.c_int32, _VP, C.c_int64, C.c_int64] + [_VP] * 7 + [C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int32]
+                    + [_VP] * 9)
 
 # name -> argtypes (after the engine handle); every function returns int
 _SIGS = {
@@ -205,6 +216,9 @@ _DEV_SIGS = {
     # reference)
     "journal_pack_dev": _JOURNAL_PACK_ARGS,
     "journal_pack": _JOURNAL_PACK_ARGS,
+    # journal compaction (include/gpx_journal_gc.h; HIP library only: tests/journal_gc_model.py is the reference)
+    "journal_gc_dev": _JOURNAL_GC_ARGS,
+    "journal_gc": _JOURNAL_GC_ARGS,
     # group images (include/gpx_image.h; HIP library only: the oracle's dump / snapshot / create are the reference)
     "group_export_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
     "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],

@@ -47,6 +47,8 @@
 #include "gpx_timers.hip.h"
 #include "../../include/gpx_journal.h"
 #include "gpx_journal.hip.h"
+#include "../../include/gpx_journal_gc.h"
+#include "gpx_journal_gc.hip.h"
 #include "../../include/gpx_checkpoint.h"
 #include "gpx_checkpoint.hip.h"
 #include "../../include/gpx_image.h"
@@ -367,6 +369,11 @@ struct gpx_engine {
   JrMem jr{};
   JrCounts* jr_counts = nullptr;
   size_t jr_stage_max = (size_t)64 << 20;
+  /* journal compaction (gpx_journal_gc_dev.inc): per-tile words, one run descriptor per row of the largest batch and the
+   * host twin's counts; one block, allocated by the first such call (jg_counts != nullptr: the marker).  The host twin's
+   * windows are bounded by jr_stage_max, which that first call reads from the environment as jr_init does */
+  JgMem jg{};
+  JgCounts* jg_counts = nullptr;
   /* checkpoint transfer (gpx_checkpoint_dev.inc): parked runs, per-tile words and the host twin's counts, inside the
    * scans' block where that is large enough, else a block of their own (cp_counts != nullptr: the marker) */
   CpMem cp{};
@@ -2424,6 +2431,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_sweep_dev.inc"
 #include "gpx_timers_dev.inc"
 #include "gpx_journal_dev.inc"
+#include "gpx_journal_gc_dev.inc"
 #include "gpx_image_dev.inc"
 #include "gpx_delta_dev.inc"
 #include "gpx_checkpoint_dev.inc"
@@ -2435,6 +2443,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_sweep_host.inc"
 #include "gpx_timers_host.inc"
 #include "gpx_journal_host.inc"
+#include "gpx_journal_gc_host.inc"
 #include "gpx_image_host.inc"
 #include "gpx_delta_host.inc"
 #include "gpx_checkpoint_host.inc"

@@ -28,6 +28,7 @@
 #include "../../include/gpx_sweep.h"
 #include "../../include/gpx_timers.h"
 #include "../../include/gpx_journal.h"
+#include "../../include/gpx_journal_gc.h"
 #include "../../include/gpx_image.h"
 #include "../../include/gpx_delta.h"
 #include "../../include/gpx_checkpoint.h"
@@ -283,6 +284,22 @@ JFN(jint, journalPack)(JNIEnv* env, jclass c, jlong h, jint n, jobject frames, j
                           B(slot), B(bnum), B(bcoord), B(rFlags), B(status), baseOffset, flags, B(out), capBytes,
                           capEntries, B(eRec), B(eGidx), B(eSlot), B(eBnum), B(eBcoord), B(eOff), B(eLen),
                           (gpx_journal_counts*)B(counts));
+}
+/* journal compaction (include/gpx_journal_gc.h): in = a direct buffer of inBytes bytes at a 16-byte boundary whose
+ * capacity is a multiple of 16 (may be null with GPX_JG_COUNT_ONLY), the seven input columns direct buffers of n entries
+ * (eBnum, eBcoord and cpSlot may be null), out = a direct buffer of capBytes bytes at a 16-byte boundary, verdict = one of
+ * n bytes or null, the seven k columns direct buffers of capEntries entries (the first five may be null), counts = one
+ * of 64 bytes.  nKeep == 0: delete the file; unchanged: leave it; else, and only with nBad == 0, write out[0, bytesDone)
+ * and rename */
+JFN(jint, journalGc)(JNIEnv* env, jclass c, jlong h, jint n, jobject in, jlong inBytes, jlong inBase, jobject eGidx,
+                     jobject eSlot, jobject eOff, jobject eLen, jobject eBnum, jobject eBcoord, jobject cpSlot,
+                     jlong outBase, jint flags, jobject out, jlong capBytes, jint capEntries, jobject verdict,
+                     jobject kSrc, jobject kGidx, jobject kSlot, jobject kBnum, jobject kBcoord, jobject kOff,
+                     jobject kLen, jobject counts) {
+  (void)c;
+  return gpx_journal_gc(H(h), n, B(in), inBytes, inBase, B(eGidx), B(eSlot), B(eOff), B(eLen), B(eBnum), B(eBcoord),
+                        B(cpSlot), outBase, flags, B(out), capBytes, capEntries, B(verdict), B(kSrc), B(kGidx), B(kSlot),
+                        B(kBnum), B(kBcoord), B(kOff), B(kLen), (gpx_journal_gc_counts*)B(counts));
 }
 /* group images (include/gpx_image.h): oRows / rows = a direct buffer of rows of gpx_image_stride bytes, counts = one
  * of 16 bytes, status = one byte per row */

@@ -10,3 +10,7 @@ from ._abi import (  # noqa: F401
     F_ACCEPTS_FROM_DISK, RETIRE_PAUSE, RETIRE_KILL,
 )
 from .checkpoint import CpCounts, checkpoint_batch, checkpoint_batch_dev, CP_PEEK, CP_ADOPT, CP_MOVED  # noqa: F401,E402
+from .viewchange import (  # noqa: F401,E402
+    PlCounts, PrlCounts, prepare_lists, prepare_lists_dev, prepare_reply_lists, prepare_reply_lists_dev,
+    prepare_reply_lists_more, prepare_reply_lists_more_dev, reply_lists_all, VCL_TILE,
+)

@@ -65,6 +65,18 @@ class ScanCounts(C.Structure):
     _fields_ = [("n_hits", C.c_int32), ("n_nogroup", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class PlCounts(C.Structure):
+    """struct gpx_pl_counts (include/gpx_viewchange.h): 32 bytes."""
+    _fields_ = [(f, C.c_int32) for f in ("n_entries", "recs_done", "entries_done", "n_dropped", "n_nack", "n_tolog")] + [
+        ("reserved", C.c_int32 * 2)]
+
+
+class PrlCounts(C.Structure):
+    """struct gpx_prl_counts (include/gpx_viewchange.h): 32 bytes."""
+    _fields_ = [(f, C.c_int32) for f in ("n_hits", "n_entries", "from_hit", "hits_done", "entries_done", "n_elected",
+                                         "n_preempted", "n_dropped")]
+
+
 class CpCounts(C.Structure):
     """struct gpx_cp_counts (include/gpx_checkpoint.h)."""
     _fields_ = [("n_adopted", C.c_int32), ("n_nogroup", C.c_int32), ("n_stopped", C.c_int32), ("n_runs", C.c_int32)]
@@ -233,6 +245,14 @@ _DEV_SIGS = {
     # oracle's commit call over the skipped slots are the reference)
     "checkpoint_batch_dev": [C.c_int32, _VP, _VP, C.c_int32] + [_VP] * 8,
     "checkpoint_batch": [C.c_int32, _VP, _VP, C.c_int32] + [_VP] * 8,
+    # the view change in list form (include/gpx_viewchange.h; HIP library only: the oracle's dense prepare_batch and
+    # prepare_reply_batch are the reference)
+    "prepare_lists_dev": [C.c_int32] + [_VP] * 9 + [C.c_int32] + [_VP] * 5,
+    "prepare_lists": [C.c_int32] + [_VP] * 9 + [C.c_int32] + [_VP] * 5,
+    "prepare_reply_lists_dev": [C.c_int32] + [_VP] * 6 + [C.c_int32] + [_VP] * 7 + [C.c_int32, C.c_int32] + [_VP] * 12,
+    "prepare_reply_lists": [C.c_int32] + [_VP] * 13 + [C.c_int32, C.c_int32] + [_VP] * 12,
+    "prepare_reply_lists_more_dev": [C.c_int32] * 3 + [_VP] * 12,
+    "prepare_reply_lists_more": [C.c_int32] * 3 + [_VP] * 12,
     "compact_last_dev": [],
     "profile_enable": [C.c_int32],
     "profile_read": [C.POINTER(GpxKernelStat), C.c_int32],

@@ -55,6 +55,8 @@
 #include "gpx_image.hip.h"
 #include "../../include/gpx_delta.h"
 #include "gpx_delta.hip.h"
+#include "../../include/gpx_viewchange.h"
+#include "gpx_vclists.hip.h"
 
 #define GPX_STAGE_N 32768 /* host-pointer calls up to this many records cross PCIe as one block each way */
 #define GPX_STAGE_BYTES ((size_t)GPX_STAGE_N * 48 + 4096)
@@ -389,6 +391,16 @@ struct gpx_engine {
    * counts; one zeroed block, allocated by the first delta export (delta_counts != nullptr: the marker) */
   DeltaMem delta{};
   DeltaCounts* delta_counts = nullptr;
+  /* view change in list form (gpx_vclists_dev.inc): the acceptor side's masks and per-tile words, and the coordinator
+   * side's dense scratch, parked hits and per-tile words - two blocks, each allocated by the first call of its side
+   * (pl_counts / prl_counts != nullptr: the markers).  prl_n: the n of the last gpx_prepare_reply_lists*, whose parked
+   * lists a continuation reads (-1: none).  vcl_stage_hits: hit rows per round of the coordinator's host twins */
+  PlMem pl{};
+  PlCounts* pl_counts = nullptr;
+  PrlMem prl{};
+  PrlCounts* prl_counts = nullptr;
+  int32_t prl_n = -1;
+  size_t vcl_stage_hits = (size_t)1 << 18;
 };
 
 namespace {
@@ -960,7 +972,7 @@ int gpx_engine_create(const gpx_config* cfg, gpx_engine** out) {
                          (const void*)k_bucket_propose<8>, (const void*)k_bucket_propose<16>,
                          (const void*)k_bucket_accept,     (const void*)k_bucket_commit,
                          (const void*)k_bucket_pack_ar,    (const void*)k_bucket_reqbatch,
-                         (const void*)k_bucket_prepare,
+                         (const void*)k_bucket_prepare<true>, (const void*)k_bucket_prepare<false>,
                          (const void*)k_bucket_prepare_reply<4, 64>,
                          (const void*)k_bucket_prepare_reply<8, 64>,
                          (const void*)k_bucket_prepare_reply<16, 64>};
@@ -2435,6 +2447,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_image_dev.inc"
 #include "gpx_delta_dev.inc"
 #include "gpx_checkpoint_dev.inc"
+#include "gpx_vclists_dev.inc"
 /* the control-plane host-pointer calls: CtlStage, then each family's twins over it and the public *_dev prototypes */
 #include "gpx_host_stage.inc"
 #include "gpx_wire_host.inc"
@@ -2447,4 +2460,5 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_image_host.inc"
 #include "gpx_delta_host.inc"
 #include "gpx_checkpoint_host.inc"
+#include "gpx_vclists_host.inc"
 #include "gpx_group_host.inc"

@@ -2097,6 +2097,9 @@ struct PrepOut {
   int32_t *p_slot, *p_bnum, *p_bcoord; /* [W][n] */
   uint8_t* status;
 };
+/* PLANES = false: the list form (gpx_vclists.hip.h) - the same evaluation, p_mask written, no planes (p_slot / p_bnum /
+ * p_bcoord are null: the lists are gathered from acc_ring, which this call does not change) */
+template <bool PLANES>
 __global__ __launch_bounds__(1024) void k_bucket_prepare(DevState S, DevScratch X, PrepOut O) {
   extern __shared__ __attribute__((aligned(16))) int32_t lds[];
   BucketView bv;
@@ -2142,10 +2145,12 @@ __global__ __launch_bounds__(1024) void k_bucket_prepare(DevState S, DevScratch 
           if (!(a.w & RF_PRESENT)) continue;
           if (jsub(a.x, first) < 0) continue;
           mask |= 1ull << w;
-          const int64_t q = (int64_t)w * O.n + ix;
-          O.p_slot[q] = a.x;
-          O.p_bnum[q] = a.y;
-          O.p_bcoord[q] = a.z;
+          if (PLANES) {
+            const int64_t q = (int64_t)w * O.n + ix;
+            O.p_slot[q] = a.x;
+            O.p_bnum[q] = a.y;
+            O.p_bcoord[q] = a.z;
+          }
         }
       }
       O.r_bnum[ix] = bn;

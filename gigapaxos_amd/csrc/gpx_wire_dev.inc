@@ -94,7 +94,7 @@ int gpx_prepare_batch_dev(gpx_engine* h, int32_t n, const int32_t* gidx, const i
   HIPCHK(hipMemsetAsync(p_mask, 0, (size_t)n * 8, e->stream));
   begin_back(e, fs, n);
   PrepOut O{n, r_bnum, r_bcoord, r_gc, r_flags, (unsigned long long*)p_mask, p_slot, p_bnum, p_bcoord, status};
-  LAUNCH_B(e, "k_bucket_prepare", k_bucket_prepare, e->S, e->X, O);
+  LAUNCH_B(e, "k_bucket_prepare", k_bucket_prepare<true>, e->S, e->X, O);
   end_call(e, fs);
   HIPCHK(hipGetLastError());
   return GPX_OK;

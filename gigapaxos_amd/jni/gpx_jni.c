@@ -32,6 +32,7 @@
 #include "../../include/gpx_image.h"
 #include "../../include/gpx_delta.h"
 #include "../../include/gpx_checkpoint.h"
+#include "../../include/gpx_viewchange.h"
 
 #ifdef GPX_HAVE_JNI
 #include <jni.h>
@@ -333,6 +334,37 @@ JFN(jint, checkpointBatch)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx,
   (void)c;
   return gpx_checkpoint_batch(H(h), n, B(gidx), B(cpSlot), flags, B(oFrom), B(oTo), B(oFlags), B(status), B(xGidx),
                               B(xFirst), B(xCount), (gpx_cp_counts*)B(counts));
+}
+/* the view change in list form (include/gpx_viewchange.h): the dense columns direct buffers of n entries, pvOff one of
+ * n + 1, the pv columns of capEntries entries, counts = one of 32 bytes; vKind / status of prepareReplyLists may be null.
+ * prepareLists' (pvOff, pvSlot, pvBnum, pvBcoord) are prepareReplyLists' pv inputs as they stand (plus a handle column) */
+JFN(jint, prepareLists)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject bnum, jobject bcoord,
+                        jobject firstSlot, jobject rBnum, jobject rBcoord, jobject rGc, jobject rFlags, jobject status,
+                        jint capEntries, jobject pvOff, jobject pvSlot, jobject pvBnum, jobject pvBcoord, jobject counts) {
+  (void)c;
+  return gpx_prepare_lists(H(h), n, B(gidx), B(bnum), B(bcoord), B(firstSlot), B(rBnum), B(rBcoord), B(rGc), B(rFlags),
+                           B(status), capEntries, B(pvOff), B(pvSlot), B(pvBnum), B(pvBcoord), (gpx_pl_counts*)B(counts));
+}
+JFN(jint, prepareReplyLists)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject acceptor, jobject rBnum,
+                             jobject rBcoord, jobject firstSlot, jobject pvOff, jobject pvSlot, jobject pvBnum,
+                             jobject pvBcoord, jobject pvHandle, jobject pvFlags, jobject vKind, jobject status,
+                             jint capHits, jint capEntries, jobject hRec, jobject hGidx, jobject hKind, jobject hStatus,
+                             jobject hMedian, jobject hOff, jobject hCount, jobject eSlot, jobject eKind, jobject eHandle,
+                             jobject eFlags, jobject counts) {
+  (void)c;
+  return gpx_prepare_reply_lists(H(h), n, B(gidx), B(acceptor), B(rBnum), B(rBcoord), B(firstSlot), B(pvOff), B(pvSlot),
+                                 B(pvBnum), B(pvBcoord), B(pvHandle), B(pvFlags), B(vKind), B(status), capHits, capEntries,
+                                 B(hRec), B(hGidx), B(hKind), B(hStatus), B(hMedian), B(hOff), B(hCount), B(eSlot),
+                                 B(eKind), B(eHandle), B(eFlags), (gpx_prl_counts*)B(counts));
+}
+JFN(jint, prepareReplyListsMore)(JNIEnv* env, jclass c, jlong h, jint fromHit, jint capHits, jint capEntries, jobject hRec,
+                                 jobject hGidx, jobject hKind, jobject hStatus, jobject hMedian, jobject hOff,
+                                 jobject hCount, jobject eSlot, jobject eKind, jobject eHandle, jobject eFlags,
+                                 jobject counts) {
+  (void)c;
+  return gpx_prepare_reply_lists_more(H(h), fromHit, capHits, capEntries, B(hRec), B(hGidx), B(hKind), B(hStatus),
+                                      B(hMedian), B(hOff), B(hCount), B(eSlot), B(eKind), B(eHandle), B(eFlags),
+                                      (gpx_prl_counts*)B(counts));
 }
 #endif /* GPX_HAVE_JNI */
 

@@ -16,7 +16,7 @@ all: $(LIB) $(CLUSTER) $(STREAMS) oracle
 $(STREAMS): gigapaxos_amd/native/gpx_streams.c
 	$(CC) -O2 -shared -fPIC -Wall -Wextra -o $@ $<
 
-$(LIB): $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc) include/gpx.h include/gpx_wire.h include/gpx_packed.h include/gpx_packed_out.h include/gpx_scan.h include/gpx_sweep.h include/gpx_timers.h include/gpx_journal.h include/gpx_journal_gc.h include/gpx_image.h include/gpx_delta.h include/gpx_checkpoint.h include/gpx_viewchange.h
+$(LIB): $(wildcard $(CSRC)/*.hip $(CSRC)/*.h $(CSRC)/*.inc) include/gpx.h include/gpx_wire.h include/gpx_packed.h include/gpx_packed_out.h include/gpx_scan.h include/gpx_sweep.h include/gpx_timers.h include/gpx_journal.h include/gpx_journal_gc.h include/gpx_logindex.h include/gpx_image.h include/gpx_delta.h include/gpx_checkpoint.h include/gpx_viewchange.h
 	cd $(CSRC) && $(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-result -o libgpx_hip.so gpx_engine.hip
 
 $(CLUSTER): $(HOST)/gpx_host.cpp $(HOST)/loopback_cluster.cpp $(HOST)/gpx_host.hpp $(LIB)

@@ -113,6 +113,12 @@ class JournalGcCounts(C.Structure):
                 + [(f, C.c_int64) for f in ("keep_bytes", "bytes_done", "named_bytes", "reserved2")])
 
 
+class LogIndexCounts(C.Structure):
+    """struct gpx_logindex_counts (include/gpx_logindex.h): 32 bytes."""
+    _fields_ = [(f, C.c_int32) for f in ("n_rows", "n_alive", "generation", "n_done", "n_hits", "n_stale", "n_nogroup",
+                                         "n_repeat")]
+
+
 class GpxPackedVotes(C.Structure):
     """struct gpx_packed_votes (include/gpx_packed.h)."""
     _fields_ = [
@@ -157,6 +163,17 @@ _JOURNAL_PACK_ARGS = ([C.c_int32, _VP, C.c_int64, C.c_int32] + [_VP] * 9 + [C.c_
 # cap_entries, verdict, the seven k_* columns, counts
 _JOURNAL_GC_ARGS = ([C.c_int32, _VP, C.c_int64, C.c_int64] + [_VP] * 7 + [C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int32]
                     + [_VP] * 9)
+
+# the log index (include/gpx_logindex.h) after the handle; a _dev call and its host twin take the same arguments
+_LOGINDEX_ARGS = {
+    "add": [C.c_int32] + [_VP] * 7 + [C.c_int32, _VP, _VP],
+    "set_gc": [C.c_int32, _VP, _VP, C.c_int32, _VP, _VP],
+    "lookup": [C.c_int32] + [_VP] * 4 + [C.c_int32] + [_VP] * 10,
+    "file_rows": [C.c_int32, C.c_int32] + [_VP] * 9,
+    "relocate": [C.c_int32, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP],
+    "files": [C.c_int32, C.c_int32, _VP, _VP, _VP, _VP],
+    "compact": [_VP],
+}
 
 # name -> argtypes (after the engine handle); every function returns int
 _SIGS = {
@@ -231,6 +248,9 @@ _DEV_SIGS = {
     # journal compaction (include/gpx_journal_gc.h; HIP library only: tests/journal_gc_model.py is the reference)
     "journal_gc_dev": _JOURNAL_GC_ARGS,
     "journal_gc": _JOURNAL_GC_ARGS,
+    # the log index (include/gpx_logindex.h; HIP library only: tests/logindex_model.py is the reference)
+    "logindex_open": [C.c_int32],
+    **{"logindex_%s%s" % (k, f): a for k, a in _LOGINDEX_ARGS.items() for f in ("_dev", "")},
     # group images (include/gpx_image.h; HIP library only: the oracle's dump / snapshot / create are the reference)
     "group_export_dev": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],
     "group_export": [C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP],

@@ -49,6 +49,8 @@
 #include "gpx_journal.hip.h"
 #include "../../include/gpx_journal_gc.h"
 #include "gpx_journal_gc.hip.h"
+#include "../../include/gpx_logindex.h"
+#include "gpx_logindex.hip.h"
 #include "../../include/gpx_checkpoint.h"
 #include "gpx_checkpoint.hip.h"
 #include "../../include/gpx_image.h"
@@ -376,6 +378,12 @@ struct gpx_engine {
    * windows are bounded by jr_stage_max, which that first call reads from the environment as jr_init does */
   JgMem jg{};
   JgCounts* jg_counts = nullptr;
+  /* log index (gpx_logindex_dev.inc): the table's two blocks of row columns, the per-group words, the header words, the
+   * scratch and the host twins' counts; one block, allocated by gpx_logindex_open (li_counts != nullptr: the index is
+   * open).  li_ub: the host's upper bound of the table's tail, which sizes the grids of the row scans */
+  LiMem li{};
+  LiCounts* li_counts = nullptr;
+  int64_t li_ub = 0;
   /* checkpoint transfer (gpx_checkpoint_dev.inc): parked runs, per-tile words and the host twin's counts, inside the
    * scans' block where that is large enough, else a block of their own (cp_counts != nullptr: the marker) */
   CpMem cp{};
@@ -2444,6 +2452,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_timers_dev.inc"
 #include "gpx_journal_dev.inc"
 #include "gpx_journal_gc_dev.inc"
+#include "gpx_logindex_dev.inc"
 #include "gpx_image_dev.inc"
 #include "gpx_delta_dev.inc"
 #include "gpx_checkpoint_dev.inc"
@@ -2457,6 +2466,7 @@ int gpx_group_dump(gpx_engine* h, int32_t gidx, int32_t* buf, int32_t cap) {
 #include "gpx_timers_host.inc"
 #include "gpx_journal_host.inc"
 #include "gpx_journal_gc_host.inc"
+#include "gpx_logindex_host.inc"
 #include "gpx_image_host.inc"
 #include "gpx_delta_host.inc"
 #include "gpx_checkpoint_host.inc"

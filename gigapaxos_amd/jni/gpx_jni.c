@@ -29,6 +29,7 @@
 #include "../../include/gpx_timers.h"
 #include "../../include/gpx_journal.h"
 #include "../../include/gpx_journal_gc.h"
+#include "../../include/gpx_logindex.h"
 #include "../../include/gpx_image.h"
 #include "../../include/gpx_delta.h"
 #include "../../include/gpx_checkpoint.h"
@@ -301,6 +302,53 @@ JFN(jint, journalGc)(JNIEnv* env, jclass c, jlong h, jint n, jobject in, jlong i
   return gpx_journal_gc(H(h), n, B(in), inBytes, inBase, B(eGidx), B(eSlot), B(eOff), B(eLen), B(eBnum), B(eBcoord),
                         B(cpSlot), outBase, flags, B(out), capBytes, capEntries, B(verdict), B(kSrc), B(kGidx), B(kSlot),
                         B(kBnum), B(kBcoord), B(kOff), B(kLen), (gpx_journal_gc_counts*)B(counts));
+}
+/* the log index (include/gpx_logindex.h): every column a direct buffer, counts = one of 32 bytes, status = one byte per
+ * record (may be null), nDev = one 32-bit count or null; files are ids the caller assigns in creation order */
+JFN(jint, logindexOpen)(JNIEnv* env, jclass c, jlong h, jint capRows) {
+  (void)env, (void)c;
+  return gpx_logindex_open(H(h), capRows);
+}
+JFN(jint, logindexAdd)(JNIEnv* env, jclass c, jlong h, jint n, jobject nDev, jobject eGidx, jobject eSlot, jobject eBnum,
+                       jobject eBcoord, jobject eOff, jobject eLen, jint file, jobject status, jobject counts) {
+  (void)c;
+  return gpx_logindex_add(H(h), n, B(nDev), B(eGidx), B(eSlot), B(eBnum), B(eBcoord), B(eOff), B(eLen), file, B(status),
+                          (gpx_logindex_counts*)B(counts));
+}
+JFN(jint, logindexSetGc)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject gcSlot, jint flags, jobject status,
+                         jobject counts) {
+  (void)c;
+  return gpx_logindex_set_gc(H(h), n, B(gidx), B(gcSlot), flags, B(status), (gpx_logindex_counts*)B(counts));
+}
+JFN(jint, logindexLookup)(JNIEnv* env, jclass c, jlong h, jint n, jobject gidx, jobject minSlot, jobject maxSlot,
+                          jobject hasMax, jint cap, jobject oRec, jobject oRow, jobject oSlot, jobject oBnum,
+                          jobject oBcoord, jobject oFile, jobject oOff, jobject oLen, jobject status, jobject counts) {
+  (void)c;
+  return gpx_logindex_lookup(H(h), n, B(gidx), B(minSlot), B(maxSlot), B(hasMax), cap, B(oRec), B(oRow), B(oSlot),
+                             B(oBnum), B(oBcoord), B(oFile), B(oOff), B(oLen), B(status),
+                             (gpx_logindex_counts*)B(counts));
+}
+JFN(jint, logindexFileRows)(JNIEnv* env, jclass c, jlong h, jint file, jint cap, jobject oRow, jobject eGidx,
+                            jobject eSlot, jobject eBnum, jobject eBcoord, jobject eOff, jobject eLen, jobject eGc,
+                            jobject counts) {
+  (void)c;
+  return gpx_logindex_file_rows(H(h), file, cap, B(oRow), B(eGidx), B(eSlot), B(eBnum), B(eBcoord), B(eOff), B(eLen),
+                                B(eGc), (gpx_logindex_counts*)B(counts));
+}
+JFN(jint, logindexRelocate)(JNIEnv* env, jclass c, jlong h, jint n, jobject nDev, jint generation, jobject oRow,
+                            jobject kSrc, jint newFile, jobject kOff, jobject kLen, jobject counts) {
+  (void)c;
+  return gpx_logindex_relocate(H(h), n, B(nDev), generation, B(oRow), B(kSrc), newFile, B(kOff), B(kLen),
+                               (gpx_logindex_counts*)B(counts));
+}
+JFN(jint, logindexFiles)(JNIEnv* env, jclass c, jlong h, jint fileBase, jint nFiles, jobject oRows, jobject oGroups,
+                         jobject oMinFile, jobject counts) {
+  (void)c;
+  return gpx_logindex_files(H(h), fileBase, nFiles, B(oRows), B(oGroups), B(oMinFile), (gpx_logindex_counts*)B(counts));
+}
+JFN(jint, logindexCompact)(JNIEnv* env, jclass c, jlong h, jobject counts) {
+  (void)c;
+  return gpx_logindex_compact(H(h), (gpx_logindex_counts*)B(counts));
 }
 /* group images (include/gpx_image.h): oRows / rows = a direct buffer of rows of gpx_image_stride bytes, counts = one
  * of 16 bytes, status = one byte per row */

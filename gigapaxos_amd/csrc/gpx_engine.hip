@@ -34,6 +34,7 @@
 #include "gpx_small.hip.h"
 #include "gpx_route.hip.h"
 #include "gpx_wire.hip.h"
+#include "gpx_bytes.hip.h"
 #include "gpx_wire_accept.hip.h"
 #include "gpx_elect.hip.h"
 #include "gpx_packed.hip.h"

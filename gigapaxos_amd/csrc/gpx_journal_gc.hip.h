@@ -3,40 +3,34 @@
 // (SQLPaxosLogger.java:3347-3440) with LogIndex.isLogMsgNeeded (LogIndex.java:331-345) decided from the acceptors' GC
 // slots in HBM.
 //
-// A call is four launches on one stream, the scheme of gpx_journal.hip.h, whose jr_scan, jr_wave_search and cap logic
-// this file uses as they are; no workgroup ever waits for another one:
+// The four launches, the caps rule, the copy's rounds, the scratch invariant and the bounds argument: gpx_bytes.hip.h.
+// What is this family's own:
 //
 //   k_jg_tile     one lane per row, GPX_JR_TILE = 256 per workgroup: the range test (every index and range BEFORE any
 //                 byte of `in` could be read), then the length prefix, then the gather of g_flags / a_gc by e_gidx, then
 //                 the verdict.  A kept row is a RUN HEAD unless row i - 1 of the same call is kept and ends exactly where
 //                 row i starts; across a tile edge row i - 1 is evaluated again.  The tile's kept entries, their bytes,
 //                 run heads, refused rows, unjudged rows and named bytes go to the per-tile words, unconditionally.
-//   k_jg_offsets  ONE workgroup: the exclusive prefixes of entries, bytes and run heads, the sums into *counts,
-//                 `unchanged`, the GPX_JG_SKIP_UNCHANGED rule, and - where a cap cuts - the first tile that does not fit
-//                 whole evaluated again, one lane per row: n_done, bytes_done and n_runs_done are exact.
-//   k_jg_rows     one workgroup per tile that has a done entry: the k_* rows, and ONE descriptor (output position, source
-//                 position) PER RUN.  A run's length is the next descriptor's position, or bytes_done for the last: a run
-//                 a cap cuts needs no length of its own.
-//   k_jg_copy     the hot one, parallel over OUTPUT bytes in 16 KB tiles like k_jr_copy, but over runs, not entries: the
-//                 source already holds the length prefixes, so inside a run the copy is a plain shifted copy - one
-//                 aligned 16-byte store from at most two aligned 16-byte loads - with no prefix synthesis and no
-//                 per-entry descriptor.  A wave-wide search finds a tile's first run; the descriptors are staged in LDS
-//                 in rounds of GPX_JR_SPAN, and a round stops in front of the chunk of its last staged descriptor
-//                 (k_jr_copy's rule: a run is at least 4 bytes, so a round moves on by at least 1,000 bytes).  Only a
-//                 chunk that straddles a run boundary, and the last partial chunk of the call, take the narrow path.
+//   k_jg_offsets  a second scan (run heads, unjudged rows, named bytes), `unchanged` and the GPX_JG_SKIP_UNCHANGED rule;
+//                 under the caps n_done, bytes_done and n_runs_done are exact.
+//   k_jg_rows     the k_* rows, and ONE descriptor (output position, source position) PER RUN.  A run's length is the
+//                 next descriptor's position, or bytes_done for the last: a run a cap cuts needs no length of its own.
+//   k_jg_copy     copy_runs over runs, not entries: the source already holds the length prefixes, so inside a run the
+//                 copy is a plain shifted copy - one aligned 16-byte store from at most two aligned 16-byte loads - with
+//                 no prefix synthesis and no per-entry descriptor (a run is at least 4 bytes, which is all the rounds
+//                 need).  Only a chunk that straddles a run boundary, and the last partial chunk of the call, take the
+//                 narrow path.
 //
 // Cache policy: `in` and `out` are touched once by the copy and go through the stream_* helpers under GPX_NT_JOURNAL;
 // the prefix test reads 4 bytes the copy reads again, the descriptors and per-tile words are hand-offs: plain.
 //
-// SCRATCH INVARIANT, as in gpx_journal.hip.h: every scratch word a call reads is one the SAME call wrote.  k_jg_offsets
-// reads the per-tile words [0, ntiles) - each written unconditionally by its tile's workgroup - and first_ok only when
-// there is a tile 0.  k_jg_rows reads tile_eoff / tile_boff / tile_hoff of its own tile (written for every tile).
-// k_jg_copy reads descriptors [0, n_runs_done): k_jg_rows wrote exactly those.
+// SCRATCH INVARIANT, beyond gpx_bytes.hip.h's: k_jg_offsets reads first_ok only when there is a tile 0; k_jg_copy reads
+// descriptors [0, n_runs_done).
 //
-// Bounds.  A descriptor index is below n_runs_done <= n_done <= n <= max_batch, the size of the descriptor columns.  A
-// row index is below n_done <= cap_entries.  An output byte is below bytes_done <= cap_bytes.  A source byte lies inside
-// a range the range test accepted, inside the window [win_lo, win_hi) that `in` holds; every aligned word that is read
-// holds at least one such byte, so nothing at or beyond in + round_up(win_hi - win_lo, 16) is read.
+// Bounds, beyond gpx_bytes.hip.h's: a descriptor index is below n_runs_done <= n_done.  A source byte lies inside a range
+// the range test accepted, inside the window [win_lo, win_hi) that `in` holds; every aligned word that is read holds at
+// least one such byte, so nothing at or beyond in + round_up(win_hi - win_lo, 16) is read.
+// Needs: gpx_bytes.hip.h, gpx_journal.hip.h (GPX_JR_TILE, GPX_JR_MAX_LEN).
 #pragma once
 
 #define GPX_JG_COUNT_ONLY_ 1     /* == GPX_JG_COUNT_ONLY of include/gpx_journal_gc.h (checked in gpx_journal_gc_dev.inc) */
@@ -89,23 +83,6 @@ struct JgRow {
   long long rel;    /* the prefix's place in the caller's block (relative to in_base); kept rows only */
 };
 
-/* four bytes at an arbitrary address, memory order, from the aligned words that hold them */
-template <bool STREAM>
-__device__ __forceinline__ uint32_t jg_load4(const uint8_t* p) {
-  const uintptr_t a = (uintptr_t)p;
-  const int32_t* q = (const int32_t*)(a & ~(uintptr_t)3);
-  const uint32_t s = (uint32_t)(a & 3);
-  uint32_t lo, hi = 0u;
-  if constexpr (STREAM) {
-    lo = (uint32_t)stream_load4<GPX_NT_JOURNAL>(q);
-    if (s) hi = (uint32_t)stream_load4<GPX_NT_JOURNAL>(q + 1);
-  } else {
-    lo = (uint32_t)q[0];
-    if (s) hi = (uint32_t)q[1];
-  }
-  return __builtin_amdgcn_alignbyte(hi, lo, s);
-}
-
 /* Row i: the range, then the prefix, then the group, then the verdict. */
 __device__ __forceinline__ JgRow jg_eval(const JgIn& I, long long i) {
   JgRow r{false, false, GPX_JG_DROP_, 0, 0};
@@ -123,7 +100,7 @@ __device__ __forceinline__ JgRow jg_eval(const JgIn& I, long long i) {
   if (urel > (unsigned long long)I.win_hi) return r;
   const long long rel = (long long)urel;
   if (L < 0 || L > GPX_JR_MAX_LEN || rel < I.win_lo || rel > I.win_hi - (4 + L)) return r;
-  if (I.in && !I.force && jg_load4<false>(I.in + (rel - I.win_lo)) != __builtin_bswap32((uint32_t)L)) return r;
+  if (I.in && !I.force && load4_unaligned<0>(I.in + (rel - I.win_lo)) != __builtin_bswap32((uint32_t)L)) return r;
   r.len = (int32_t)L;
   r.rel = rel;
   r.keep = true;
@@ -170,8 +147,8 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_jg_tile(JgIn I, JgMem M, uint8_t*
   const bool head = jg_head(I, i, r);
   const bool bad = r.valid && r.v == GPX_JG_BAD_, usable = r.valid && !bad;
   if (verdict && r.valid) verdict[i] = r.v;
-  const JrScan S = jr_scan(r.keep, bad, r.keep ? 4ll + r.len : 0ll);
-  const JrScan H = jr_scan(head, r.valid && r.v == GPX_JG_KEEP_UNJUDGED_, usable ? 4ll + r.len : 0ll);
+  const Scan64 S = block_scan64(r.keep, bad, r.keep ? 4ll + r.len : 0ll);
+  const Scan64 H = block_scan64(head, r.valid && r.v == GPX_JG_KEEP_UNJUDGED_, usable ? 4ll + r.len : 0ll);
   if (threadIdx.x == 0) {
     M.tile_cnt[blockIdx.x] = S.tot_c;
     M.tile_bad[blockIdx.x] = S.tot_b;
@@ -187,10 +164,7 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_jg_tile(JgIn I, JgMem M, uint8_t*
 __global__ __launch_bounds__(GPX_BLOCK) void k_jg_offsets(int32_t ntiles, JgIn I, JgMem M, long long cap_bytes,
                                                          int32_t cap_entries, int32_t flags, long long in_bytes,
                                                          JgCounts* __restrict__ counts) {
-  __shared__ int32_t w_cut[GPX_JR_WAVES], s_cut_e, s_cut_h;
-  __shared__ long long s_cut_b;
-  const int32_t lane = (int32_t)threadIdx.x & 63, wave = (int32_t)threadIdx.x >> 6;
-  int32_t run_c = 0, run_h = 0, run_bad = 0, run_unj = 0, cut = INT32_MAX, cut_e = 0, cut_h = 0;
+  int32_t run_c = 0, run_h = 0, run_bad = 0, run_unj = 0, cut = INT32_MAX, cut_x[2] = {0, 0}; /* entries, heads */
   long long run_v = 0, run_named = 0, cut_b = 0;
   for (int32_t t0 = 0; t0 < ntiles; t0 += GPX_BLOCK) {
     const int32_t t = t0 + (int32_t)threadIdx.x;
@@ -198,45 +172,33 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_jg_offsets(int32_t ntiles, JgIn I
     const int32_t c = live ? M.tile_cnt[t] : 0, b = live ? M.tile_bad[t] : 0;
     const int32_t hd = live ? M.tile_heads[t] : 0, u = live ? M.tile_unj[t] : 0;
     const long long v = live ? M.tile_bytes[t] : 0, nm = live ? M.tile_named[t] : 0;
-    const JrScan S = jr_scan(c, b, v);
-    const JrScan H = jr_scan(hd, u, nm);
+    const Scan64 S = block_scan64(c, b, v);
+    const Scan64 H = block_scan64(hd, u, nm);
     const int32_t eo = run_c + S.ex_c, ho = run_h + H.ex_c; /* <= n: fit */
     const long long bo = run_v + S.ex_v;
     if (live) {
       M.tile_eoff[t] = eo;
       M.tile_boff[t] = bo;
       M.tile_hoff[t] = ho;
-      /* the first tile that is not done whole; a lane's tiles come in ascending order */
-      if (c > 0 && cut == INT32_MAX && (eo + c > cap_entries || bo + v > cap_bytes)) cut = t, cut_e = eo, cut_b = bo, cut_h = ho;
+      /* a lane's tiles come in ascending order */
+      if (cut == INT32_MAX && caps_cut(c, v, eo, bo, cap_entries, cap_bytes)) cut = t, cut_x[0] = eo, cut_b = bo, cut_x[1] = ho;
     }
     run_c += S.tot_c, run_bad += S.tot_b, run_v += S.tot_v;
     run_h += H.tot_c, run_unj += H.tot_b, run_named += H.tot_v;
   }
-  int32_t first = cut;
-#pragma unroll
-  for (int32_t d = 1; d < 64; d <<= 1) first = min(first, __shfl_xor(first, d));
-  if (lane == 0) w_cut[wave] = first;
-  __syncthreads();
-#pragma unroll
-  for (int32_t q = 0; q < GPX_JR_WAVES; q++) first = min(first, w_cut[q]);
+  const int32_t first = caps_first_cut(cut, cut_b, cut_x);
   int32_t n_done = run_c, runs_done = run_h;
   long long bytes_done = run_v;
   if (first != INT32_MAX) { /* the same in every lane */
-    if (cut == first) s_cut_e = cut_e, s_cut_b = cut_b, s_cut_h = cut_h;
-    __syncthreads();
-    const int32_t e0 = s_cut_e, h0 = s_cut_h;
-    const long long b0 = s_cut_b;
     const long long i = (long long)first * GPX_JR_TILE + (long long)threadIdx.x;
     const JgRow r = jg_eval(I, i);
     const bool head = jg_head(I, i, r);
     const long long v = r.keep ? 4ll + r.len : 0ll;
-    const JrScan S = jr_scan(r.keep, 0, v);
-    /* done entries are a prefix: positions and ends only grow */
-    const bool done = r.keep && e0 + S.ex_c < cap_entries && b0 + S.ex_v + v <= cap_bytes;
-    const JrScan D = jr_scan(done, done && head, done ? v : 0ll);
-    n_done = e0 + D.tot_c;
-    bytes_done = b0 + D.tot_v;
-    runs_done = h0 + D.tot_b;
+    const bool done = caps_done(r.keep, v, cut_x[0], cut_b, cap_entries, cap_bytes);
+    const Scan64 D = block_scan64(done, done && head, done ? v : 0ll);
+    n_done = cut_x[0] + D.tot_c;
+    bytes_done = cut_b + D.tot_v;
+    runs_done = cut_x[1] + D.tot_b;
   }
   /* every row kept and adjacent to its predecessor: one run (none for no rows) that starts at in_base and is the block */
   const bool unchanged = run_bad == 0 && run_c == I.n && run_h == (I.n > 0 ? 1 : 0) && (I.n == 0 || *M.first_ok) && run_v == in_bytes;
@@ -251,8 +213,8 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_jg_rows(JgIn I, JgMem M, JgOut O,
   const long long i = (long long)blockIdx.x * GPX_JR_TILE + (long long)threadIdx.x;
   const JgRow r = jg_eval(I, i);
   const bool head = jg_head(I, i, r);
-  const JrScan S = jr_scan(r.keep, 0, r.keep ? 4ll + r.len : 0ll);
-  const JrScan H = jr_scan(head, 0, 0ll);
+  const Scan64 S = block_scan64(r.keep, 0, r.keep ? 4ll + r.len : 0ll);
+  const Scan64 H = block_scan64(head, 0, 0ll);
   const int32_t e = e0 + S.ex_c;
   if (!r.keep || e >= n_done) return;
   const long long pos = M.tile_boff[blockIdx.x] + S.ex_v;
@@ -279,102 +241,50 @@ __device__ __forceinline__ uint32_t jg_pick(int32_t dw, int32_t a, int32_t b, in
   return (uint32_t)(dw == 0 ? a : dw == 1 ? b : dw == 2 ? c : d);
 }
 
-__global__ __launch_bounds__(GPX_BLOCK) void k_jg_copy(const uint8_t* __restrict__ in, JgMem M, uint8_t* __restrict__ out,
-                                                      const JgCounts* __restrict__ counts) {
-  __shared__ JgTile T;
-  __shared__ int32_t s_first;
-  const long long lim = counts->bytes_done;
-  const int32_t nR = counts->n_runs_done;
-  for (long long base = (long long)blockIdx.x * GPX_JR_CTILE; base < lim; base += (long long)gridDim.x * GPX_JR_CTILE) {
-    const long long end = base + GPX_JR_CTILE < lim ? base + GPX_JR_CTILE : lim;
-    if (threadIdx.x < 64) {
-      const int32_t j0 = jr_wave_search(M.d_pos, nR, base); /* pos(0) = 0 <= base: never -1 */
-      if (threadIdx.x == 0) s_first = j0 < 0 ? 0 : j0;
+struct JgCopy { /* copy_runs' family: one descriptor per done run */
+  typedef JgTile Tile;
+  const uint8_t* in;
+  const JgMem& M;
+  __device__ __forceinline__ void stage(JgTile& T, int32_t e, int32_t s) const { T.src[s] = M.d_src[e]; }
+  __device__ __forceinline__ void chunk(const JgTile& T, long long P, long long Pe, int32_t k, int32_t ns,
+                                        uint32_t (&w)[4]) const {
+    if (Pe == P + 16 && (k + 1 >= ns || T.pos[k + 1] >= Pe)) {
+      /* the chunk lies inside run k: sixteen source bytes from the one or two aligned words that hold them */
+      const long long s = T.src[k] + (P - T.pos[k]);
+      const int32_t sh = (int32_t)(s & 15), dw = sh >> 2;
+      const uint32_t b = (uint32_t)(sh & 3);
+      const I4* q = (const I4*)(in + (s - sh));
+      const I4 A = stream_load16<GPX_NT_JOURNAL>(q);
+      I4 B = mk4(0, 0, 0, 0);
+      if (sh) B = stream_load16<GPX_NT_JOURNAL>(q + 1); /* holds byte s + 15 */
+      const uint32_t y0 = jg_pick(dw, A.x, A.y, A.z, A.w), y1 = jg_pick(dw, A.y, A.z, A.w, B.x);
+      const uint32_t y2 = jg_pick(dw, A.z, A.w, B.x, B.y), y3 = jg_pick(dw, A.w, B.x, B.y, B.z);
+      const uint32_t y4 = jg_pick(dw, B.x, B.y, B.z, B.w);
+      w[0] = __builtin_amdgcn_alignbyte(y1, y0, b), w[1] = __builtin_amdgcn_alignbyte(y2, y1, b);
+      w[2] = __builtin_amdgcn_alignbyte(y3, y2, b), w[3] = __builtin_amdgcn_alignbyte(y4, y3, b);
+      return;
     }
-    __syncthreads();
-    int32_t j = s_first; /* the run that holds byte lo */
-    long long lo = base;
-    while (lo < end) { /* rounds: lo, hi, j and ns are the same in every lane */
-      const int32_t e = j + (int32_t)threadIdx.x;
-      bool staged = false;
-      if (e < nR) {
-        const long long p = M.d_pos[e];
-        staged = p < end;
-        if (staged) {
-          T.pos[threadIdx.x] = p;
-          T.src[threadIdx.x] = M.d_src[e];
-        }
-      }
-      const int32_t ns = __syncthreads_count(staged); /* positions ascend: the staged ones are the first ns */
-      /* a full round may be cut short by what is not staged: stop in front of the chunk of its last descriptor */
-      long long hi = end;
-      if (ns == GPX_JR_SPAN) {
-        const long long h = T.pos[GPX_JR_SPAN - 1] & ~15ll; /* >= pos[1] + 4 * (SPAN - 2) - 15 > lo */
-        hi = h < hi ? h : hi;
-      }
-      for (long long P = lo + 16 * (long long)threadIdx.x; P < hi; P += 16 * GPX_BLOCK) {
-        int32_t k = 0, kh = ns; /* the last staged run with pos <= P: pos[0] <= lo <= P */
-        while (kh - k > 1) {
-          const int32_t mid = (k + kh) >> 1;
-          if (T.pos[mid] <= P) k = mid;
-          else kh = mid;
-        }
-        const long long Pe = P + 16 < end ? P + 16 : end;
-        uint32_t w0, w1, w2, w3;
-        if (Pe == P + 16 && (k + 1 >= ns || T.pos[k + 1] >= Pe)) {
-          /* the chunk lies inside run k: sixteen source bytes from the one or two aligned words that hold them */
-          const long long s = T.src[k] + (P - T.pos[k]);
-          const int32_t sh = (int32_t)(s & 15), dw = sh >> 2;
-          const uint32_t b = (uint32_t)(sh & 3);
-          const I4* q = (const I4*)(in + (s - sh));
-          const I4 A = stream_load16<GPX_NT_JOURNAL>(q);
-          I4 B = mk4(0, 0, 0, 0);
-          if (sh) B = stream_load16<GPX_NT_JOURNAL>(q + 1); /* holds byte s + 15 */
-          const uint32_t y0 = jg_pick(dw, A.x, A.y, A.z, A.w), y1 = jg_pick(dw, A.y, A.z, A.w, B.x);
-          const uint32_t y2 = jg_pick(dw, A.z, A.w, B.x, B.y), y3 = jg_pick(dw, A.w, B.x, B.y, B.z);
-          const uint32_t y4 = jg_pick(dw, B.x, B.y, B.z, B.w);
-          w0 = __builtin_amdgcn_alignbyte(y1, y0, b), w1 = __builtin_amdgcn_alignbyte(y2, y1, b);
-          w2 = __builtin_amdgcn_alignbyte(y3, y2, b), w3 = __builtin_amdgcn_alignbyte(y4, y3, b);
-        } else {
-          /* a run boundary inside the chunk, or the last chunk of the call: dword by dword, byte by byte at a boundary */
-          uint32_t w[4];
+    /* a run boundary inside the chunk, or the last chunk of the call: dword by dword, byte by byte at a boundary */
 #pragma unroll
-          for (int32_t d = 0; d < 4; d++) {
-            const long long Q = P + 4 * d;
-            w[d] = 0u;
-            if (Q >= Pe) continue;
-            while (k + 1 < ns && T.pos[k + 1] <= Q) k++;
-            if (Q + 4 <= Pe && (k + 1 >= ns || T.pos[k + 1] >= Q + 4)) {
-              w[d] = jg_load4<true>(in + T.src[k] + (Q - T.pos[k]));
-            } else {
-              for (int32_t c = 0; c < 4 && Q + c < Pe; c++) {
-                while (k + 1 < ns && T.pos[k + 1] <= Q + c) k++;
-                w[d] |= (uint32_t)in[T.src[k] + (Q + c - T.pos[k])] << (8 * c);
-              }
-            }
-          }
-          w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-        }
-        if (Pe == P + 16) {
-          stream_store16<GPX_NT_JOURNAL>((I4*)(out + P), mk4((int32_t)w0, (int32_t)w1, (int32_t)w2, (int32_t)w3));
-        } else { /* the last chunk of the call: nothing at or beyond out + bytes_done */
-          const uint32_t w[4] = {w0, w1, w2, w3};
-#pragma unroll
-          for (int32_t d = 0; d < 4; d++) {
-            const long long Q = P + 4 * d;
-            if (Q + 4 <= end) {
-              stream_store4<GPX_NT_JOURNAL>((uint32_t*)(out + Q), w[d]);
-            } else {
-              for (int32_t c = 0; c < 4; c++)
-                if (Q + c < end) out[Q + c] = (uint8_t)(w[d] >> (8 * c));
-            }
-          }
+    for (int32_t d = 0; d < 4; d++) {
+      const long long Q = P + 4 * d;
+      w[d] = 0u;
+      if (Q >= Pe) continue;
+      while (k + 1 < ns && T.pos[k + 1] <= Q) k++;
+      if (Q + 4 <= Pe && (k + 1 >= ns || T.pos[k + 1] >= Q + 4)) {
+        w[d] = load4_unaligned<GPX_NT_JOURNAL>(in + T.src[k] + (Q - T.pos[k]));
+      } else {
+        for (int32_t c = 0; c < 4 && Q + c < Pe; c++) {
+          while (k + 1 < ns && T.pos[k + 1] <= Q + c) k++;
+          w[d] |= (uint32_t)in[T.src[k] + (Q + c - T.pos[k])] << (8 * c);
         }
       }
-      /* the next round starts at the run that holds byte hi; T is restaged only after every lane is here */
-      const int32_t below = __syncthreads_count((int32_t)threadIdx.x < ns && T.pos[threadIdx.x] <= hi);
-      j += below - 1;
-      lo = hi;
     }
   }
+};
+
+__global__ __launch_bounds__(GPX_BLOCK) void k_jg_copy(const uint8_t* __restrict__ in, JgMem M, uint8_t* __restrict__ out,
+                                                      const JgCounts* __restrict__ counts) {
+  copy_runs(JgCopy{in, M}, M.d_pos, counts->n_runs_done, out, counts->bytes_done);
 }
+

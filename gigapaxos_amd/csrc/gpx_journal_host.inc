@@ -58,7 +58,7 @@ int gpx_journal_pack(gpx_engine* h, int32_t n, const uint8_t* frames, int64_t fr
     c.bcoord = bcoord ? t.in(bcoord + i0, mm) : nullptr;
     c.r_flags = t.in(r_flags + i0, mm);
     c.status = t.in(status + i0, mm);
-    /* the window, its first byte at a 256-byte boundary; jr_load4 may read the whole aligned word of the last byte */
+    /* the window, its first byte at a 256-byte boundary; k_jr_copy may read the whole aligned word of the last byte */
     uint8_t* d_fr = (uint8_t*)t.tmp_bytes((size_t)(hi - lo) + 4, 1, false);
     c.base_offset = base_offset + tot.n_bytes; /* == bytes_done as long as nothing is cut */
     c.flags = pack ? 0 : GPX_JR_COUNT_ONLY;

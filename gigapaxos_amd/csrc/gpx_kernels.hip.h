@@ -89,8 +89,9 @@ __host__ __device__ __forceinline__ I4 mk4(int32_t x, int32_t y, int32_t z, int3
 #define GPX_NT_PROPOSE 4  /* k_propose_one / k_propose_pers: the five output columns */
 #define GPX_NT_PLACE 8    /* k_bucket_ar16_tiles*: the in-place decision columns */
 #define GPX_NT_STAGE 16   /* k_bucket_ar16_tiles*: the decision staging, when the in-place columns are written too (off) */
-#define GPX_NT_JOURNAL 32 /* k_jr_copy (gpx_journal.hip.h): the frame bytes it reads and the journal bytes it writes (on by
-                           * the rule above - touched once; not measured against the plain form) */
+#define GPX_NT_JOURNAL 32 /* copy_runs (gpx_bytes.hip.h) in k_jr_copy and k_jg_copy: the source bytes they read and the
+                           * journal bytes they write (on by the rule above - touched once; not measured against the
+                           * plain form) */
 #ifndef GPX_NT_STREAMS
 #define GPX_NT_STREAMS (GPX_NT_VOTES | GPX_NT_PROPOSE | GPX_NT_PLACE | GPX_NT_JOURNAL)
 #endif

@@ -23,6 +23,9 @@
  *                  with a wave-wide 64-ary search, stages the descriptors of what it overlaps in LDS, and
  *                  every lane assembles 16-byte chunks from unaligned source dwords (v_alignbyte) into
  *                  aligned dwordx4 stores.  Pad bytes are zero, so every output dword belongs to one frame.
+ *                  The searches and the unaligned load are gpx_bytes.hip.h's (wave_search, lds_search,
+ *                  load4_unaligned); the loop is this kernel's own: one round, two descriptor lists, padded
+ *                  frames, the `fit` rule.
  *
  * A frame is a concatenation of regions, each a byte range of one REQUEST frame with dword-sized patches:
  *   leader   bytes [0, E) of the leader frame; [4, 8) = ACCEPT; flattened: [h, h + 4) = be32(total),
@@ -380,44 +383,6 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_acc_rank(AccIn I, AccScratch X, A
   X.fpos[F.fseg + rank] = O.frame_off[f] + F.E + bytes;
 }
 
-/* last index in [0, n) with a[index] <= key, or -1 (a ascending); the whole wave takes part, 64 samples
- * per round: log64(n) dependent loads */
-__device__ __forceinline__ int32_t acc_wave_search(const long long* __restrict__ a, int32_t n, long long key) {
-  const int32_t lane = threadIdx.x & 63;
-  int32_t lo = -1, hi = n;
-  while (hi - lo > 1) {
-    const int32_t step = (hi - lo - 1 + 63) / 64;
-    const int32_t idx = lo + 1 + lane * step;
-    const bool le = idx < hi && a[idx] <= key;
-    const int32_t c = __popcll(__ballot(le));
-    const int32_t cand = lo + 1 + c * step;
-    if (c > 0) lo = lo + 1 + (c - 1) * step;
-    hi = cand < hi ? cand : hi;
-  }
-  return lo;
-}
-
-/* last index in [0, n) of an LDS array with s[index] <= key (s[0] <= key) */
-__device__ __forceinline__ int32_t acc_lds_search(const long long* s, int32_t n, long long key) {
-  int32_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (s[mid] <= key) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-/* four bytes at an arbitrary address, memory order: the aligned words that hold them + v_alignbyte (no
- * word is read that holds none of the four) */
-__device__ __forceinline__ uint32_t acc_load4(const uint8_t* p) {
-  const uintptr_t a = (uintptr_t)p;
-  const uint32_t* q = (const uint32_t*)(a & ~(uintptr_t)3);
-  const uint32_t s = (uint32_t)(a & 3);
-  const uint32_t lo = q[0];
-  const uint32_t hi = s ? q[1] : 0u;
-  return __builtin_amdgcn_alignbyte(hi, lo, s);
-}
 __device__ __forceinline__ uint32_t acc_be_byte(int32_t v, int32_t k) { /* byte k of be32(v) */
   return ((uint32_t)v >> (24 - 8 * k)) & 0xffu;
 }
@@ -443,7 +408,7 @@ __device__ __forceinline__ uint32_t acc_byte(const AccTile& T, const AccIn& I, i
   if (q < len - GPX_WA_TAIL) {
     if (T.nk == 0) return 0u; /* (cannot happen: the tile staged the pieces it overlaps) */
     const long long P = T.off[j] + q;
-    const int32_t k = acc_lds_search(T.kpos, T.nk, P);
+    const int32_t k = lds_search(T.kpos, T.nk, P);
     const int32_t r = (int32_t)(P - T.kpos[k]), h = T.kh[k];
     if (r < 0 || r >= 4 + T.ke[k]) return 0u;
     if (r < 4) return acc_be_byte(h + 4, r);
@@ -465,12 +430,12 @@ __device__ __forceinline__ uint32_t acc_dword(const AccTile& T, const AccIn& I, 
   if (q == 4) return __builtin_bswap32((uint32_t)GPX_WT_ACCEPT);
   if (q + 4 <= E) {
     const int32_t H = T.H[j];
-    if (H < 0 || q + 4 <= H || q >= H + 4) return acc_load4(I.frames + T.src[j] + q);
+    if (H < 0 || q + 4 <= H || q >= H + 4) return load4_unaligned<0>(I.frames + T.src[j] + q);
   } else if (q >= E && q + 4 <= len - GPX_WA_TAIL && T.nk > 0) {
     const long long P = T.off[j] + q;
-    const int32_t k = acc_lds_search(T.kpos, T.nk, P);
+    const int32_t k = lds_search(T.kpos, T.nk, P);
     const int32_t r = (int32_t)(P - T.kpos[k]), h = T.kh[k];
-    if (r >= 4 && r + 4 <= 4 + T.ke[k] && (r + 4 <= 4 + h || r >= 8 + h)) return acc_load4(I.frames + T.ksrc[k] + r - 4);
+    if (r >= 4 && r + 4 <= 4 + T.ke[k] && (r + 4 <= 4 + h || r >= 8 + h)) return load4_unaligned<0>(I.frames + T.ksrc[k] + r - 4);
   }
   uint32_t w = 0;
 #pragma unroll
@@ -488,8 +453,8 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_acc_copy(AccIn I, AccScratch X, A
   for (long long base = (long long)blockIdx.x * GPX_WA_TILE; base < lim; base += (long long)gridDim.x * GPX_WA_TILE) {
     const long long end = base + GPX_WA_TILE < lim ? base + GPX_WA_TILE : lim;
     if (threadIdx.x < 64) {
-      const int32_t f0 = acc_wave_search(O.frame_off, nF, base);
-      const int32_t k0 = acc_wave_search(X.fpos, nK, base);
+      const int32_t f0 = wave_search(O.frame_off, nF, base);
+      const int32_t k0 = wave_search(X.fpos, nK, base);
       if (threadIdx.x == 0) {
         s_first[0] = f0 < 0 ? 0 : f0;
         s_first[1] = k0 < 0 ? 0 : k0;
@@ -536,7 +501,7 @@ __global__ __launch_bounds__(GPX_BLOCK) void k_acc_copy(AccIn I, AccScratch X, A
     for (int c = 0; c < GPX_WA_TILE / (16 * GPX_BLOCK); c++) {
       const long long P = base + (long long)c * (16 * GPX_BLOCK) + 16 * (long long)threadIdx.x;
       if (P >= end) break;
-      int32_t j = acc_lds_search(T.off, nf, P);
+      int32_t j = lds_search(T.off, nf, P);
       uint32_t w[4];
       bool wr[4];
 #pragma unroll

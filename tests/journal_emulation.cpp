@@ -1,9 +1,9 @@
 // Lockstep CPU emulation of the kernels of gigapaxos_amd/csrc/gpx_journal.hip.h (tests/test_journal_abi.py compiles and
-// runs this with AddressSanitizer): the real header, unmodified.  One std::thread per lane of a workgroup, barriers for
-// __syncthreads and for the wave collectives, one workgroup at a time.  Every buffer is a heap block of its exact size
-// (`frames` rounded up to 4 bytes: jr_load4 reads whole aligned words), the scratch starts as garbage and `out` and the
-// rows carry a sentinel, so an index past an end is a sanitizer report and a byte written beyond what is done a
-// failure.  The launches and their conditions are those of jr_run (gpx_journal_dev.inc).  The expected answer is a plain
+// runs this with AddressSanitizer): the real header, unmodified, on top of the real gpx_bytes.hip.h.  One std::thread
+// per lane of a workgroup, barriers for __syncthreads and for the wave collectives, one workgroup at a time.  Every
+// buffer is a heap block of its exact size (`frames` rounded up to 4 bytes: load4_unaligned reads whole aligned words),
+// the scratch starts as garbage and `out` and the rows carry a sentinel, so an index past an end is a sanitizer report
+// and a byte written beyond what is done a failure.  The launches and their conditions are those of jr_run (gpx_journal_dev.inc).  The expected answer is a plain
 // loop over the rules of include/gpx_journal.h.  What this cannot show is what only the GPU has: the compiler's code and
 // memory ordering between launches (tests/test_journal_gpu.py).
 #include <algorithm>
@@ -35,6 +35,7 @@ template <int BIT> static int32_t stream_load4(const int32_t* p) { return *p; }
 template <int BIT, class T> static void stream_store4(T* p, T v) { *p = v; }
 template <int BIT> static void stream_store16(I4* p, I4 v) { *p = v; }
 
+#include "gpx_bytes.hip.h"
 #include "gpx_journal.hip.h"
 
 template <class T> static T* blk_of(const std::vector<T>& v) {

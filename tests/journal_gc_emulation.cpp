@@ -1,6 +1,6 @@
 // Lockstep CPU emulation of the kernels of gigapaxos_amd/csrc/gpx_journal_gc.hip.h (tests/test_journal_gc_abi.py
-// compiles and runs this with AddressSanitizer): the real header, unmodified, on top of the real gpx_journal.hip.h whose
-// scan and search it uses.  One std::thread per lane of a workgroup, one workgroup at a time (tests/lockstep_runtime.h).
+// compiles and runs this with AddressSanitizer): the real header, unmodified, on top of the real gpx_bytes.hip.h and
+// gpx_journal.hip.h.  One std::thread per lane of a workgroup, one workgroup at a time (tests/lockstep_runtime.h).
 // Every buffer is a heap block of its exact size - `in` rounded up to 16 bytes, which is the read contract of
 // include/gpx_journal_gc.h - the scratch starts as garbage and `out`, the verdicts and the rows carry a sentinel, so an
 // index past an end is a sanitizer report and a byte written beyond what is done a failure.  The launches and their
@@ -35,6 +35,7 @@ template <int BIT> static I4 stream_load16(const I4* p) { return *p; }
 template <int BIT, class T> static void stream_store4(T* p, T v) { *p = v; }
 template <int BIT> static void stream_store16(I4* p, I4 v) { *p = v; }
 
+#include "gpx_bytes.hip.h"
 #include "gpx_journal.hip.h"
 #include "gpx_journal_gc.hip.h"
 

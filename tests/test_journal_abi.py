@@ -170,3 +170,20 @@ def test_jr_kernels_in_lockstep_emulation_under_asan(tmp_path):
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 84 and all(": ok" in ln for ln in lines), out.stdout
+
+
+def test_byte_run_core_in_lockstep_emulation_under_asan(tmp_path):
+    """tests/bytes_emulation.cpp: the pieces of gpx_bytes.hip.h as they are, one thread per lane, each against a plain
+    loop - the wave-wide search at 0, 1, 63, 64, 65, 4,096 and 4,097 positions, the LDS search, the unaligned load at the
+    end of a block at each alignment, the copy skeleton under the smallest family (tile edges +- 5, 4,097 descriptors in
+    a tile, a run over three tiles, every tail, more tiles than the grid, nothing), the caps helpers cut by entries and
+    by bytes in tile 0 and in tile 257 - every buffer of its exact size under AddressSanitizer and UBSan.  A stand-alone
+    program: nothing is loaded into Python."""
+    exe = str(tmp_path / "bytes_emulation")
+    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-pthread", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "gigapaxos_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "bytes_emulation.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.strip().splitlines() == ["wave_search: ok", "lds_search: ok", "load4_unaligned: ok", "copy_runs: ok",
+                                               "caps: ok"], out.stdout
